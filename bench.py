@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- QB3M_FTL encode+decode throughput of the MI355X-native QB3 library.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: the command above starts its N ranks itself; python -m torch.distributed.run --nnodes=1 --nproc-per-node N ...
      bench.py --gpus N ..., what the driver runs, works as well)
+
+A plain run sets up, warms up, times the K steps (no profiler events inside them) and prints the headline line.  Everything
+else described below -- the checks against the reference's anchors and of both decode flavours, the per-kernel table and
+roofline, the other table level, the sustained leg, plain containers, the host API, the other configurations and the CPU
+baselines -- runs only with --full.  --dump-outputs DIR writes what the last timed step computed (a fixed, seeded sample of the
+container and of the decoded raster, float32 .npy files, about 36 MB) so that two builds can be compared output for output.
 
 N = 1 -- BASELINE.json configs[1]: ONE 16384x16384 3-band uint8 raster (NOISY3, seed 2), resident in HBM before the
 clock starts.  A step = qb3x_encode_device (the container, self-indexed: the restart table travels INSIDE it as
@@ -316,6 +322,11 @@ def main():
     ap.add_argument("--tiles-per-rank", type=int, default=32)
     ap.add_argument("--batch-tiles", type=int, default=8)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: reference checks, kernel table and roofline, the other table level, sustained leg, plain "
+                         "containers, host API, the other configurations and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a seeded sample of what the last step computed as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -378,52 +389,61 @@ def main():
     img = synth.generate(W, H, bands, dtype, "NOISY3", 2, device=dev)
     raw = img.reshape(-1).view(torch.uint8)
     raw_bytes = raw.numel()
-    # the step's encoder writes the self-indexed container and nothing beside it (d_index = NULL); a second handle writes the
-    # out-of-band index once, for the decode flavour that is reported next to the headline
+    # the step's encoder writes the self-indexed container and nothing beside it (d_index = NULL); with --full a second handle
+    # writes the out-of-band index once, for the decode flavour that is reported next to the headline
     enc = qdev.DeviceEncoder(W, H, bands, dtype, mode=qb3_amd.QB3M_FTL, want_index=False, index_chunk=args.table_level)
     out = torch.empty(raw_bytes, dtype=torch.uint8, device=dev)
     dst, n, _ = enc.encode(img)
-    enc_oob = qdev.DeviceEncoder(W, H, bands, dtype, mode=qb3_amd.QB3M_FTL, want_index=True, index_chunk=args.table_level)
-    dst_oob, n_oob, index = enc_oob.encode(img)
-    if n_oob != n or not torch.equal(dst_oob[:n], dst[:n]):
-        sys.exit("bench.py: the container depends on whether an out-of-band index is asked for")
-    oob_index_bytes = enc_oob.index_bytes
-    index = index.clone()
-    del dst_oob, enc_oob
-    torch.cuda.empty_cache()
+    if args.full:
+        enc_oob = qdev.DeviceEncoder(W, H, bands, dtype, mode=qb3_amd.QB3M_FTL, want_index=True, index_chunk=args.table_level)
+        dst_oob, n_oob, index = enc_oob.encode(img)
+        if n_oob != n or not torch.equal(dst_oob[:n], dst[:n]):
+            sys.exit("bench.py: the container depends on whether an out-of-band index is asked for")
+        oob_index_bytes = enc_oob.index_bytes
+        index = index.clone()
+        del dst_oob, enc_oob
+        torch.cuda.empty_cache()
     dec = qdev.DeviceDecoder(dst, n)
+    last_n = [n]
 
     def step():
-        enc.encode(img)                                  # container (self-indexed) -> enc.dst
+        last_n[0] = enc.encode(img)[1]                   # container (self-indexed) -> enc.dst
         dec.decode(dst, out=out, index=None)             # decode from the container alone
 
-    # ---- correctness first: bit identity with the reference (size AND hash), both decode flavours exact
-    host = dst[:n].cpu().numpy()
-    ident, fnv = (None, None)
-    if args.size == 16384:
-        ident, fnv = container_check(qb3_amd, np, host, "c2")
-        if not ident:
-            sys.exit(f"bench.py: container (minus its table chunks) hashes to {fnv}, the reference's to {ANCHORS['c2'][1]} -- not bit-identical")
-    stream_bytes = ANCHORS["c2"][0] if args.size == 16384 else n
-    for ix in (None, index):
-        out.zero_()
-        dec.decode(dst, out=out, index=ix)
-        if not torch.equal(out, raw):
-            sys.exit("bench.py: decode(encode(x)) != x -- refusing to report a number")
+    if args.full:
+        # ---- correctness first: bit identity with the reference (size AND hash), both decode flavours exact
+        host = dst[:n].cpu().numpy()
+        ident, fnv = (None, None)
+        if args.size == 16384:
+            ident, fnv = container_check(qb3_amd, np, host, "c2")
+            if not ident:
+                sys.exit(f"bench.py: container (minus its table chunks) hashes to {fnv}, the reference's to {ANCHORS['c2'][1]} -- not bit-identical")
+        stream_bytes = ANCHORS["c2"][0] if args.size == 16384 else n
+        for ix in (None, index):
+            out.zero_()
+            dec.decode(dst, out=out, index=ix)
+            if not torch.equal(out, raw):
+                sys.exit("bench.py: decode(encode(x)) != x -- refusing to report a number")
     for _ in range(max(1, args.warmup)):
         step()
 
-    # ---- the timed region: HIP events around the two coding kernels only -- the dominant kernel is one of them (level 3: an event
-    # pair costs the stream about 15 us, more than the microsecond kernels take and a tenth of the concatenation; those are timed in
-    # two extra, untimed steps afterwards)
+    # ---- the timed region.  --full: HIP events around the two coding kernels only -- the dominant kernel is one of them (level 3: an
+    # event pair costs the stream about 15 us, more than the microsecond kernels take and a tenth of the concatenation; those are timed
+    # in two extra, untimed steps afterwards).  A plain run records no events.
     prof = Prof(qdev)
-    prof.start(3)
+    if args.full:
+        prof.start(3)
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, dst[:last_n[0]], out)
+    if not args.full:
+        print(json.dumps(headline(args, W, H, dt, {"table_level": args.table_level, "container_bytes": int(last_n[0])})))
+        return
     timed = prof.stop()
     prof.start(1)
     for _ in range(2):
@@ -586,20 +606,10 @@ def main():
             workloads.update(run_other(wl, args, torch, qb3_amd, synth, qdev, dev))
 
     cpu = None if args.no_cpu_baseline else cpu_baseline()
-    line = {
-        "metric": "MPixel/s encode+decode (QB3M_FTL, 8-bit 3-band)",
-        "value": round(W * H / (dt / args.steps) / 1e6, 1),
-        "unit": "MPixel/s",
-        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "u8", "data": "synthetic",
-        "config": {"workload": f"{W}x{H}x3 uint8 NOISY3 seed 2; QB3M_FTL qb3x_encode_device (self-indexed container, table level {args.table_level}) + "
-                               "qb3x_decode_device of that container alone (index = NULL, restart table inside the container)",
-                   "table_level": args.table_level, "table_bytes": table_bytes(host),
-                   "stream_bytes": stream_bytes, "ratio": round(stream_bytes / raw_bytes, 4), "container_bytes": int(n),
-                   "bit_identical_to_reference": ident, "fnv1a64_without_table_chunks": fnv},
-        "value_uses": "decode_from_container",
+    line = headline(args, W, H, dt, {"table_level": args.table_level, "table_bytes": table_bytes(host),
+                                     "stream_bytes": stream_bytes, "ratio": round(stream_bytes / raw_bytes, 4), "container_bytes": int(n),
+                                     "bit_identical_to_reference": ident, "fnv1a64_without_table_chunks": fnv})
+    line.update({
         "encode_MPixel_s_kernels": round(W * H / enc_ms / 1e3, 1) if enc_ms else None,
         "decode_MPixel_s_kernels": round(W * H / dec_ms / 1e3, 1) if dec_ms else None,
         "decode": {"from_container_ms_kernels": round(dec_ms, 4), "out_of_band_index_ms_kernels": round(oob_ms, 4),
@@ -612,8 +622,51 @@ def main():
         "cpu_baseline": cpu,
         "host_api_ms": host_api,
         "workloads": workloads,
-    }
+    })
     print(json.dumps(line))
+
+
+def headline(args, W, H, dt, config):
+    """the fields of the N = 1 line that a plain run and --full share; dt: seconds of the args.steps timed steps"""
+    return {
+        "metric": "MPixel/s encode+decode (QB3M_FTL, 8-bit 3-band)",
+        "value": round(W * H / (dt / args.steps) / 1e6, 1),
+        "unit": "MPixel/s",
+        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u8", "data": "synthetic",
+        "config": {"workload": f"{W}x{H}x3 uint8 NOISY3 seed 2; QB3M_FTL qb3x_encode_device (self-indexed container, table level {args.table_level}) + "
+                               "qb3x_decode_device of that container alone (index = NULL, restart table inside the container)", **config},
+        "value_uses": "decode_from_container",
+    }
+
+
+DUMP_SAMPLE = 1 << 22       # bytes of each large output written by --dump-outputs (as float32: 16 MB a file)
+DUMP_HEAD = 1 << 20         # leading container bytes written whole (header and restart-table chunks)
+
+
+def dump_outputs(path, torch, container, decoded, sizes=None, seed=20261016):
+    """--dump-outputs: what a caller of the timed step receives -- the container sizes (float64; sizes: of the containers
+    that lie back to back in `container`, default one), the first DUMP_HEAD container bytes, and the bytes of the container(s)
+    and of the decoded raster(s) at DUMP_SAMPLE positions drawn from a fixed seed (sorted; the positions depend only on the seed
+    and the length sampled), float32"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def sample(t, salt):
+        n = t.numel()
+        if n <= DUMP_SAMPLE:
+            return t.float().cpu().numpy()
+        pos = np.sort(np.random.default_rng([seed, salt]).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+        return t[torch.from_numpy(pos).to(t.device)].float().cpu().numpy()
+
+    files = {"container_sizes": np.array(sizes or [container.numel()], dtype=np.float64),
+             "container_head": container[:DUMP_HEAD].float().cpu().numpy(),
+             "container_sample": sample(container, 1),
+             "decoded_sample": sample(decoded, 2)}
+    for name, a in files.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def host_api_times(qb3_amd, img, W, H, table_level):
@@ -757,34 +810,35 @@ def run_tiles_multi(args, torch, dist, qb3_amd, synth, qdev, tiles, dev, rank, w
         return got
 
     got = step()
-    torch.cuda.synchronize()
-    if not torch.equal(out, imgs):
-        sys.exit("bench.py: decode(encode(x)) != x -- refusing to report a number")
-    # What arrived at the root is what the senders made: every rank hashes its own containers (FNV-1a64, the library's),
-    # the hashes are gathered, the root hashes every container it received and compares; rank 0's own tiles 1000 / 1001 are
-    # checked against the reference's anchors (size + FNV without the table chunks).  Untimed.
-    import numpy as np
-    host_all = tc.dst[:count * tc.pitch].cpu().numpy()
-    mine = [qb3_amd.fnv(host_all[t * tc.pitch:t * tc.pitch + int(tc.sizes[t])]) for t in range(count)]
-    everyone = [None] * world
-    dist.all_gather_object(everyone, mine)
-    intact, anchors_ok = None, None
-    if rank == 0:
-        intact, checked = True, 0
-        for b, (bufs, size_lists, offset_lists) in enumerate(got):
-            lo = batches[b][0]
-            for r in range(1, world):
-                hb = bufs[r].cpu().numpy() if bufs[r] is not None else None
-                for t, (sz, off) in enumerate(zip(size_lists[r], offset_lists[r])):     # (a peer's containers arrive packed back to back)
-                    ok = hb is not None and qb3_amd.fnv(hb[off:off + int(sz)]) == everyone[r][lo + t]
-                    intact, checked = intact and ok, checked + 1
-        intact = bool(intact and checked == (world - 1) * count)
-        anchors_ok = all(container_check(qb3_amd, np, host_all[t * tc.pitch:t * tc.pitch + int(tc.sizes[t])], tag)[0]
-                         for t, tag in ((0, "c5_tile1000"), (1, "c5_tile1001")) if t < count)
-        if not (intact and anchors_ok):
-            sys.exit(f"bench.py: gathered containers differ from the senders' (intact={intact}) or rank 0's tiles from the reference's anchors "
-                     f"(anchors={anchors_ok}) -- refusing to report a number")
-    del host_all
+    if args.full:
+        torch.cuda.synchronize()
+        if not torch.equal(out, imgs):
+            sys.exit("bench.py: decode(encode(x)) != x -- refusing to report a number")
+        # What arrived at the root is what the senders made: every rank hashes its own containers (FNV-1a64, the library's),
+        # the hashes are gathered, the root hashes every container it received and compares; rank 0's own tiles 1000 / 1001 are
+        # checked against the reference's anchors (size + FNV without the table chunks).  Untimed.
+        import numpy as np
+        host_all = tc.dst[:count * tc.pitch].cpu().numpy()
+        mine = [qb3_amd.fnv(host_all[t * tc.pitch:t * tc.pitch + int(tc.sizes[t])]) for t in range(count)]
+        everyone = [None] * world
+        dist.all_gather_object(everyone, mine)
+        intact, anchors_ok = None, None
+        if rank == 0:
+            intact, checked = True, 0
+            for b, (bufs, size_lists, offset_lists) in enumerate(got):
+                lo = batches[b][0]
+                for r in range(1, world):
+                    hb = bufs[r].cpu().numpy() if bufs[r] is not None else None
+                    for t, (sz, off) in enumerate(zip(size_lists[r], offset_lists[r])):     # (a peer's containers arrive packed back to back)
+                        ok = hb is not None and qb3_amd.fnv(hb[off:off + int(sz)]) == everyone[r][lo + t]
+                        intact, checked = intact and ok, checked + 1
+            intact = bool(intact and checked == (world - 1) * count)
+            anchors_ok = all(container_check(qb3_amd, np, host_all[t * tc.pitch:t * tc.pitch + int(tc.sizes[t])], tag)[0]
+                             for t, tag in ((0, "c5_tile1000"), (1, "c5_tile1001")) if t < count)
+            if not (intact and anchors_ok):
+                sys.exit(f"bench.py: gathered containers differ from the senders' (intact={intact}) or rank 0's tiles from the reference's anchors "
+                         f"(anchors={anchors_ok}) -- refusing to report a number")
+        del host_all
     for _ in range(max(1, args.warmup) - 1):
         step()
 
@@ -800,6 +854,26 @@ def run_tiles_multi(args, torch, dist, qb3_amd, synth, qdev, tiles, dev, rank, w
         return float(t.item())
 
     dt = timed(True)
+    px = total * w * h
+    line = {
+        "metric": "MPixel/s encode+decode (QB3M_FTL, 8-bit 3-band)",
+        "value": round(px / (dt / args.steps) / 1e6, 1),
+        "unit": "MPixel/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u8", "data": "synthetic",
+        "config": {"workload": f"{total} independent 4096x4096x3 uint8 NOISY3 tiles (seeds 1000..), {args.tiles_per_rank} per GPU, QB3M_FTL: qb3x_encode_tiles in batches of "
+                               f"{nb}, containers gathered on rank 0 ({'RCCL send/recv' if args.backend == 'nccl' else args.backend + ' rehearsal'}) beside the coding "
+                               "of the next batch, qb3x_decode_tiles of every rank's own tiles from the containers alone (index = NULL; every tile carries its restart table, level 1: 0.7 % on top of the stream -- the step is bound by the gather, bytes on the link cost more than the decoder's walk); the gather is inside the step",
+                   "tiles_total": total, "tiles_per_gpu": args.tiles_per_rank, "parallelism": f"tiles sharded over {world} GPUs, no data-path collective but the gather"},
+    }
+    if args.dump_outputs and rank == 0:                  # rank 0's own tiles: its containers back to back, its decoded tiles
+        sizes_0 = [int(s) for s in tc.sizes[:count]]
+        dump_outputs(args.dump_outputs, torch, torch.cat([tc.dst[t * tc.pitch:t * tc.pitch + s] for t, s in enumerate(sizes_0)]),
+                     out.reshape(-1).view(torch.uint8), sizes_0)
+    if not args.full:
+        return line
     prof = Prof(qdev)                                    # rank 0's kernels, over the coding-only leg
     if rank == 0:
         prof.start()
@@ -826,26 +900,14 @@ def run_tiles_multi(args, torch, dist, qb3_amd, synth, qdev, tiles, dev, rank, w
     bytes_root = None
     if rank == 0:
         bytes_root = sum(sum(sl) for (_, sls, _) in got for sl in sls[1:])
-    px = total * w * h
-    line = {
-        "metric": "MPixel/s encode+decode (QB3M_FTL, 8-bit 3-band)",
-        "value": round(px / (dt / args.steps) / 1e6, 1),
-        "unit": "MPixel/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "u8", "data": "synthetic",
-        "config": {"workload": f"{total} independent 4096x4096x3 uint8 NOISY3 tiles (seeds 1000..), {args.tiles_per_rank} per GPU, QB3M_FTL: qb3x_encode_tiles in batches of "
-                               f"{nb}, containers gathered on rank 0 ({'RCCL send/recv' if args.backend == 'nccl' else args.backend + ' rehearsal'}) beside the coding "
-                               "of the next batch, qb3x_decode_tiles of every rank's own tiles from the containers alone (index = NULL; every tile carries its restart table, level 1: 0.7 % on top of the stream -- the step is bound by the gather, bytes on the link cost more than the decoder's walk); the gather is inside the step",
-                   "tiles_total": total, "tiles_per_gpu": args.tiles_per_rank, "parallelism": f"tiles sharded over {world} GPUs, no data-path collective but the gather"},
+    line.update({
         "coding_only": {"ms_per_step": round(dt_code / args.steps * 1e3, 3), "MPixel_s": round(px / (dt_code / args.steps) / 1e6, 1)},
         "gather": {"bytes_into_root_per_step": bytes_root, "GBps_into_root": round(bytes_root / (dt / args.steps) / 1e9, 1) if bytes_root else None,
                    "containers_intact": intact, "check": "FNV-1a64 of every container received at the root against its sender's; rank 0's tiles 1000 and 1001 against the reference's anchors",
                    "tiles_1000_1001_match_reference": anchors_ok, "backend": "nccl (RCCL) send/recv" if args.backend == "nccl" else args.backend + " (rehearsal)"},
         "roofline": roofline,
         "cpu_baseline": None if (args.no_cpu_baseline or rank != 0) else cpu_baseline_tiles(),
-    }
+    })
     return line
 
 

@@ -1,14 +1,14 @@
 #!/bin/bash
 # profiles/collect.sh TAG -- the rocprofv3 runs behind profiles/TAG_* (run on the GPU box from the repo root).
 # Counters are collected in their own passes with --kernel-trace only (no sys/hip/hsa tracing next to --pmc).
-# TAG_*: BASELINE configs[1] alone (bench.py --no-workloads): kernel trace, FETCH_SIZE, WRITE_SIZE and SQ passes.
+# TAG_*: BASELINE configs[1] alone (bench.py --full --no-workloads): kernel trace, FETCH_SIZE, WRITE_SIZE and SQ passes.
 # TAG_c2best / TAG_c3 / TAG_c4 / TAG_c5 / TAG_plain: the other configurations (bench.py --workload ...): kernel trace and
 # the same FETCH_SIZE, WRITE_SIZE and SQ passes (TAG_<wl>_pmc_hbm.csv, TAG_<wl>_sq.csv;
 # pmc_traffic.json keeps them under the workload's name in bench.py's `workloads`).  WORKLOADS="c2best c3" limits the list.
 set -e
 TAG=${1:-rXX}
 OUT=gpurun_out/prof_$TAG
-CMD="bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-workloads"
+CMD="bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-workloads"
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$OLDPWD}"
 mkdir -p $OUT
 if [ -z "$SKIP_C2" ]; then      # (SKIP_C2=1: only the workloads named in WORKLOADS)

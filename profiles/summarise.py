@@ -188,7 +188,7 @@ def main():
     if stats_only:
         sys.argv.pop(1)
     tag, trace_dir = sys.argv[1:3]
-    cmd = os.environ.get("PROFILE_CMD", "python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline")
+    cmd = os.environ.get("PROFILE_CMD", "python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline")
     stats = kernel_stats(trace_dir)
     with open(os.path.join(HERE, tag + "_kernel_stats.csv"), "w") as f:
         f.write("# rocprofv3 --kernel-trace --stats -- %s   (MI355X)\n" % cmd)
