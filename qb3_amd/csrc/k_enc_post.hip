@@ -61,6 +61,46 @@ __device__ __forceinline__ uint32_t ff_pairs_in(uint32_t v) {
     return (uint32_t)__popc(((t & 0x7f7f7fu) + 0x010101u) & t & 0x808080u);
 }
 
+// The table workgroups of enc_concat_kernel (a.ix_coder): chunk c of the restart table, whose entries the coding kernel wrote with
+// chunk-relative positions.  The positions become stream positions (the segment's chunk is 64 k / PX_NBP); the head, the "zz" pad
+// chunk and, behind the last chunk, "DT" are written; the check of the entries (ix_seal_kernel's) is the sum over the bytes as the coder
+// left them, read before anything here is written, corrected for the position bytes each thread rewrites.
+__device__ __forceinline__ void ix_finish_chunk(const EncArgs &a, uint32_t c) {
+    typedef uint32_t u32_a1 __attribute__((aligned(1)));
+    __shared__ uint32_t part[4];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t here = (a.ix_K - c * a.ix_per_chunk < a.ix_per_chunk) ? a.ix_K - c * a.ix_per_chunk : a.ix_per_chunk;
+    uint8_t *chunk = a.ix_dst + (uint64_t)c * (IX_HEAD + IX_PAD + (uint64_t)a.ix_per_chunk * a.ix_E);
+    uint8_t *e0 = chunk + IX_HEAD;
+    uint32_t s = ix_sum_part<4>(e0, here * a.ix_E, tid, 256);
+    __syncthreads();                                        // (every byte is read before any is written)
+    for (uint32_t j = tid; j < here; j += 256) {
+        uint8_t *e = e0 + (uint64_t)j * a.ix_E;
+        const uint32_t rel = *(const u32_a1 *)e;
+        const uint64_t k = (uint64_t)c * a.ix_per_chunk + j;
+        const uint64_t bp = chunk_start(a, (uint32_t)(k * 64 / PX_NBP)) + rel;
+#pragma unroll
+        for (uint32_t i = 0; i < 6; i++) {
+            const uint32_t nb = (uint32_t)(bp >> (8 * i)) & 0xffu, ob = i < 4 ? (rel >> (8 * i)) & 0xffu : 0u;
+            s += (nb - ob) * ((j * a.ix_E + i) * 0x9e3779b1u + 1u);
+            e[i] = (uint8_t)nb;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) s += (uint32_t)__shfl_xor((int)s, d, 64);
+    if ((tid & 63) == 0) part[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) {
+        const uint32_t len = IX_HEAD + here * a.ix_E, f = ix_sum_fold(part[0] + part[1] + part[2] + part[3]);
+        chunk[0] = 'i'; chunk[1] = 'x'; chunk[2] = (uint8_t)len; chunk[3] = (uint8_t)(len >> 8);
+        chunk[4] = 3; chunk[5] = 2; chunk[6] = (uint8_t)f; chunk[7] = (uint8_t)(f >> 8);
+        for (uint32_t i = 0; i < 4; i++) chunk[8 + i] = (uint8_t)(a.ix_blocks >> (8 * i));
+        uint8_t *pad = chunk + len;
+        pad[0] = 'z'; pad[1] = 'z'; pad[2] = 4; pad[3] = 0;
+        if (c * a.ix_per_chunk + here == a.ix_K) { pad[4] = 'D'; pad[5] = 'T'; }
+    }
+}
+
 // Concatenate: one WAVE per chunk reads the chunk's slot, funnel-shifts it to its bit position and stores the
 // dwords that lie wholly inside the chunk; the first and last shifted dword go to the seam table.
 // With zrun_probe (the RLE0 modes) the wave also counts, among the dwords it moves, the positions at which four zero bytes
@@ -72,9 +112,11 @@ __device__ __forceinline__ uint32_t ff_pairs_in(uint32_t v) {
 // zero: on the side of running the pass, and config 2's QB3M_BEST stream, which has no zero run at all, came out with 5 401 -- one
 // chunk boundary in twelve -- and paid 0.2 ms for the size pass every call.)  Pairs of 0xff are counted too rarely (never across
 // dwords, never in bits another chunk owns): on the side of running the pass.
+// The first a.ix_wgs workgroups finish the chunks of a restart table the coding kernel wrote (ix_finish_chunk) instead.
 __global__ void __launch_bounds__(256) enc_concat_kernel(const EncArgs a0) {
     const EncArgs a = enc_for_tile(a0, blockIdx.y);
-    const uint32_t chunk = a.chunk0 + blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (blockIdx.x < a.ix_wgs) { ix_finish_chunk(a, blockIdx.x); return; }
+    const uint32_t chunk = a.chunk0 + (blockIdx.x - a.ix_wgs) * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (chunk >= a.chunk_end) return;
     const uint64_t G = (uint64_t)a.out_bit0 + chunk_start(a, chunk);
     const uint32_t total = a.chunk_bits[chunk];
@@ -247,7 +289,7 @@ __global__ void __launch_bounds__(256) enc_finish_kernel(const EncArgs a0) {
             const uint64_t v = a.idx.bitpos[sgi];
             const uint64_t bp = chunk_start(a, (uint32_t)(v >> 32)) + (v & 0xffffffffu);
             a.idx.bitpos[sgi] = bp;
-            if (!a.ix_dst || sgi % a.ix_spe) continue;
+            if (!a.ix_dst || a.ix_coder || sgi % a.ix_spe) continue;       // (a table the coding kernel wrote: enc_concat_kernel's)
             const uint32_t ke = (uint32_t)(sgi / a.ix_spe);        // the segment's entry of the restart table
             const uint32_t c = ke / a.ix_per_chunk, j = ke - c * a.ix_per_chunk;
             const uint32_t here = (a.ix_K - c * a.ix_per_chunk < a.ix_per_chunk) ? a.ix_K - c * a.ix_per_chunk : a.ix_per_chunk;   // entries of this chunk
@@ -529,6 +571,7 @@ __global__ void __launch_bounds__(256) ix_seal_kernel(const EncArgs a0) {
 }
 
 static void launch_enc_tables(const EncArgs &a, hipStream_t st);
+static uint32_t ix_table_chunks(const EncArgs &a) { return a.ix_dst ? (a.ix_K + a.ix_per_chunk - 1) / a.ix_per_chunk : 0; }
 void launch_enc_post(const EncArgs &a, const EncPlan &plan, hipStream_t st) {
     const uint32_t nt = a.ntiles;
     {
@@ -537,7 +580,9 @@ void launch_enc_post(const EncArgs &a, const EncPlan &plan, hipStream_t st) {
     }
     {
         ProfScope ps("enc_concat", st);
-        hipLaunchKernelGGL(enc_concat_kernel, dim3((plan.nchunks + 3) / 4, nt), dim3(256), 0, st, a);
+        EncArgs b = a;
+        b.ix_wgs = a.ix_coder ? ix_table_chunks(a) : 0;
+        hipLaunchKernelGGL(enc_concat_kernel, dim3((plan.nchunks + 3) / 4 + b.ix_wgs, nt), dim3(256), 0, st, b);
     }
     ProfScope ps("enc_seams", st);
     {       // boundaries, stream length, index positions, the restart table's entries and chunk heads, the header: one launch
@@ -568,6 +613,12 @@ void launch_enc_post_tail(const EncArgs &a, const EncPlan &plan, hipStream_t st)
 }
 static void launch_enc_tables(const EncArgs &a, hipStream_t st) {
     const uint32_t nt = a.ntiles;
+    if (a.ix_coder) {       // entries from the coding kernel: what is left of the table is enc_concat_kernel's work (one-shot: its own launch)
+        EncArgs b = a;
+        b.ix_wgs = ix_table_chunks(a);
+        if (a.finish_what == 2 && b.ix_wgs) hipLaunchKernelGGL(enc_concat_kernel, dim3(b.ix_wgs, nt), dim3(256), 0, st, b);
+        return;
+    }
     if (a.ix_dst && a.have_idx && a.ix_bl && lane_per_unit_shape(a.g.tsz, a.g.mode, a.g.bands)) {       // a field per unit (k_dec_pxu.hip)
         if (a.g.mode == CM_BEST) hipLaunchKernelGGL(ix_blu_best_fill_kernel, dim3((uint32_t)(((uint64_t)a.ix_K * 16 + 255) / 256), nt), dim3(256), 0, st, a);
         else {

@@ -3,7 +3,47 @@
 
 namespace qb3dev {
 
-// Codes the chunk whose blocks the lanes hold (lane 0: the halo block) into the LDS bit buffer, from bit 0; the
+// The level-2 restart table's entries of the chunk's blocks, written in place (layout: ix_bl_fill_kernel, k_enc_post.hip; an entry per
+// 64-block index segment).  A group of four blocks is five bytes of ten-bit lengths: the group's first lane writes them, with its
+// neighbours' lengths from a DPP quad permute (a chunk holds whole groups: PX_NBP).  The lane of a segment's first block writes the
+// entry's fixed part, the position chunk-relative: enc_concat_kernel's table workgroups make it a stream position.  bl: the block's
+// bits (0 for lanes without a payload block).  Every lane must be active.
+template <int B>
+__device__ __forceinline__ void px_table_entries(const EncArgs &a, uint32_t chunk, bool payload, uint32_t gblk, uint32_t bl, uint32_t pos,
+                                                 uint32_t prp, const uint32_t (&pvv)[B]) {
+    static_assert(IX_BL_BITS == 10 && PX_NBP % 4 == 0, "groups of four fields are five bytes, a chunk holds whole groups");
+    typedef uint32_t u32_a1 __attribute__((aligned(1)));
+    const uint32_t tid = threadIdx.x;
+    const uint32_t l1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bl, 0x55, 0xf, 0xf, false);     // quad_perm:[1,1,1,1]
+    const uint32_t l2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bl, 0xaa, 0xf, 0xf, false);     // quad_perm:[2,2,2,2]
+    const uint32_t l3 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bl, 0xff, 0xf, 0xf, false);     // quad_perm:[3,3,3,3]
+    const uint64_t cover = (uint64_t)a.ix_K * 64;          // blocks the entries cover (the last one may reach past the raster)
+    // the entries a workgroup touches (at most six: PX_NBP + 64 blocks) lie in at most two table chunks: one division a workgroup
+    const uint32_t k0 = (uint32_t)((uint64_t)chunk * PX_NBP / 64), c0 = k0 / a.ix_per_chunk, j0 = k0 - c0 * a.ix_per_chunk;
+    auto entry = [&](uint32_t k) {
+        uint32_t c = c0, j = j0 + (k - k0);
+        if (j >= a.ix_per_chunk) { c++; j -= a.ix_per_chunk; }
+        return a.ix_dst + (uint64_t)c * (IX_HEAD + IX_PAD + (uint64_t)a.ix_per_chunk * a.ix_E) + IX_HEAD + (uint64_t)j * a.ix_E;
+    };
+    const uint64_t g0 = (uint64_t)chunk * PX_NBP + tid;
+    if ((tid & 3) == 0 && tid < PX_NBP && g0 < cover) {
+        const uint64_t bits = (uint64_t)bl | (uint64_t)l1 << 10 | (uint64_t)l2 << 20 | (uint64_t)l3 << 30;
+        uint8_t *e = entry((uint32_t)(g0 >> 6)) + 6 + 2 * B + 5 * (uint32_t)((g0 >> 2) & 15);
+        *(u32_a1 *)e = (uint32_t)bits; e[4] = (uint8_t)(bits >> 32);
+    }
+    if (payload && (gblk & 63) == 0) {
+        uint8_t *e = entry(gblk >> 6);
+        *(u32_a1 *)e = pos; e[4] = 0; e[5] = 0;
+#pragma unroll
+        for (int c = 0; c < B; c++) { e[6 + c] = (uint8_t)((prp >> (4 * c)) & 15u); e[6 + B + c] = (uint8_t)pvv[c]; }
+    }
+    if (chunk + 1 == a.nchunks && tid < 16) {              // the last entry's groups behind the last chunk: no blocks, zero lengths
+        const uint64_t z = (uint64_t)(chunk + 1) * PX_NBP + 4 * tid;
+        if (z < cover) { uint8_t *e = entry((uint32_t)(z >> 6)) + 6 + 2 * B + 5 * (uint32_t)((z >> 2) & 15); *(u32_a1 *)e = 0; e[4] = 0; }
+    }
+}
+
+// Codes the chunk whose blocks the lanes hold (the last lane: the halo block) into the LDS bit buffer, from bit 0; the
 // buffer must be zero.  total: bits of the chunk; pos: where the lane's block starts.
 template <int B, bool RGB, uint64_t ORDER, bool STEP>
 __device__ __forceinline__ void px_code_chunk(const EncArgs &a, const EncArgs &a0, uint32_t chunk, bool valid, bool payload, uint32_t gblk,
@@ -12,7 +52,7 @@ __device__ __forceinline__ void px_code_chunk(const EncArgs &a, const EncArgs &a
     constexpr uint32_t UMASK = 7;
     const uint32_t nblocks = (uint32_t)a.g.nblocks;
     PxFront<B> f;
-    px_front<B, RGB, ORDER>(a0, gblk, w, pd, etab, wsum, tabv, f);
+    px_front<B, RGB, ORDER, true>(a0, gblk, w, pd, etab, wsum, tabv, f);
     const uint32_t rp_packed = f.rp_packed, prp = f.prp;
 
     // ---- per band: the unit's bit string as six pieces of at most 27 bits; pl = piece length (low byte)
@@ -31,8 +71,10 @@ __device__ __forceinline__ void px_code_chunk(const EncArgs &a, const EncArgs &a
             blen[0] += lens[c];
         }
     }
+    const uint32_t bl = blen[0];
     block_exscan_dpp<1>(blen, wsum);
     pos = blen[0]; total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    if (a.ix_coder) px_table_entries<B>(a, chunk, payload, gblk, bl, pos, prp, f.pvv);
 
     if (payload) {
         LdsWriter32 wr;
@@ -83,8 +125,10 @@ __global__ void __launch_bounds__(256, 4) enc_px_kernel(const EncArgs a0) {
     const uint32_t etab_off = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t *)smem;
 
     const uint32_t chunk = a.chunk0 + blockIdx.x;      // (chunk0: the first chunk of this launch -- 0 but for the strips of a pipelined host call)
-    const int64_t gs = (int64_t)chunk * 255 - 1 + tid;     // lane 0 is the halo block
-    const bool valid = gs >= 0 && gs < (int64_t)nblocks, payload = valid && tid >= 1;
+    // lanes 0 .. PX_NBP - 1: the chunk's blocks; the last lane: the halo block, the one in front of them (its rungs are what the
+    // first block is entered with)
+    const int64_t gs = tid < PX_NBP ? (int64_t)chunk * PX_NBP + tid : tid == 255 ? (int64_t)chunk * PX_NBP - 1 : -1;
+    const bool valid = gs >= 0 && gs < (int64_t)nblocks, payload = valid && tid < PX_NBP;
     const uint32_t gblk = valid ? (uint32_t)gs : 0u;
     uint32_t w[4][B], pd, total, pos;
     px_load_block<B, ORDER>(a, valid, gblk, w, pd);

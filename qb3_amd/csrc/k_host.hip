@@ -302,8 +302,8 @@ EncPlan plan_encode(const Geometry &g) {
         return p;
     }
     if (p.px) {
-        p.threads = 256; p.slots = 256; p.nbp = 255;
-        p.nchunks = (uint32_t)((g.nblocks + 254) / 255);
+        p.threads = 256; p.slots = 256; p.nbp = g.mode == CM_BEST ? 255 : PX_NBP;      // (FTL/BASE: whole four-block groups a chunk)
+        p.nchunks = (uint32_t)((g.nblocks + p.nbp - 1) / p.nbp);
         const EncWs L = enc_ws_layout(g, p.nchunks, p.nbp, p.threads);
         p.lds_bytes = (g.mode == CM_BEST ? PXB_LDS_FIXED : 2048 + 256) + 4 * (size_t)L.slot_dw;
         p.ws_bytes = L.total;
@@ -381,9 +381,13 @@ static bool make_enc_args(EncArgs &a, const Geometry &g, const EncPlan &plan, co
     a.px_aligned = !(g.w & 3) && !((g.stride * g.tsz) & 3) && !((uintptr_t)img & 3) && !(tb.src_pitch & 3);
     a.res = (EncResult *)(w + L.res);
     a.st = st_in;
-    a.have_idx = index != nullptr;
-    a.idx_no_ulen = index && ix.base && ix.own_index && !ix.block_lens;      // (block lengths are sums of the unit lengths)
     a.ix_bl = ix.base && ix.block_lens;
+    // the 8-bit FTL/BASE lane-per-block coder writes a level-2 table itself (entry = index segment of 64 blocks); the library's own
+    // index is then not needed at all
+    a.ix_coder = a.ix_bl && plan.px && g.tsz == 1 && g.mode != CM_BEST && g.seg_blocks == 64 && ix.blocks == 64;
+    a.ix_wgs = 0;
+    a.have_idx = index != nullptr && !(a.ix_coder && ix.own_index);
+    a.idx_no_ulen = index && ix.base && ix.own_index && !ix.block_lens;      // (block lengths are sums of the unit lengths)
     a.idx = index ? index_view(g, index) : IndexView{nullptr, nullptr, nullptr, nullptr, nullptr};
     if (g.tsz != 1 && g.tsz != 2 && g.tsz != 4 && g.tsz != 8) { set_error("encode: bad value size", 0); return false; }
     return true;

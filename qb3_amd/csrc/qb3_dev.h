@@ -117,6 +117,9 @@ struct EncPlan {
     bool pxw_best;          // ... its front end under the common-factor analysis (k_enc_best.hip, FRONT = 1 / 2)
 };
 EncPlan plan_encode(const Geometry &g);
+// payload blocks a chunk of the 8-bit FTL/BASE lane-per-block encoder (k_enc_px.hip) codes: a multiple of four, so that every
+// four-block group of a level-2 restart table entry (five bytes) belongs to one workgroup, which writes it
+constexpr uint32_t PX_NBP = 252;
 constexpr uint32_t PXB_LDS_FIXED = 11664;      // LDS of the 8-bit common-factor lane-per-block encoder in front of its bit buffer
 
 // Optional restart table carried INSIDE the container as ignorable chunks ("ix", include/qb3x.h): K entries, one per

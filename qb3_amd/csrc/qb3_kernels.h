@@ -217,6 +217,9 @@ struct EncArgs {
     uint32_t ix_K, ix_spe, ix_E;    //   ... entries, fine segments per entry, bytes per entry
     uint32_t ix_bl;                 //   ... entries end with their segment's block lengths (IX_BL_BITS bits each)
     uint32_t ix_per_chunk, ix_blocks;   // ... entries per chunk, blocks per entry
+    uint32_t ix_coder;              //   ... written by the coding kernel (enc_px_kernel, entries of 64 blocks with block lengths): the
+                                    //   entries with chunk-relative positions; enc_concat_kernel's first ix_wgs workgroups finish them
+    uint32_t ix_wgs;                //   ... enc_concat_kernel: leading workgroups, one per table chunk (positions, head, pad, check)
     EncResult *res;
     BandState st;
     IndexView idx;
@@ -345,6 +348,8 @@ struct DecArgs {
 // entry bytes folded to 16 bits (a table sits in an ignorable chunk the format does not protect; its positions, rungs and
 // values are taken as truth by the decoder, so a damaged table must be told from a good one: the decoder then falls back
 // to the plain walk).  part = this thread's share of the sum over bytes [0, n) of `e`, thread t of nthr taking i = t, t + nthr, ...
+// U: sixteen-byte loads a thread has in flight at once
+template <int U = 1>
 __device__ __forceinline__ uint32_t ix_sum_part(const uint8_t *e, uint32_t n, uint32_t t, uint32_t nthr) {
     // sum over i in [0, n) of (e[i] + 1) * (i * K + 1), K = 0x9e3779b1 (mod 2^32).  The bytes are read sixteen at a time from
     // the aligned address at or below e (a table starts wherever the header ends); bytes outside [0, n) do not count.
@@ -352,14 +357,20 @@ __device__ __forceinline__ uint32_t ix_sum_part(const uint8_t *e, uint32_t n, ui
     const uint4 *base = (const uint4 *)(e - off);
     const uint32_t nvec = (off + n + 15) >> 4;
     uint32_t s = 0;
-    for (uint32_t v = t; v < nvec; v += nthr) {
-        const uint4 q = base[v];
-        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+    for (uint32_t v0 = t; v0 < nvec; v0 += U * nthr) {
+        uint4 q[U];
 #pragma unroll
-        for (uint32_t k = 0; k < 16; k++) {
-            const uint32_t i = 16 * v + k - off;            // (wraps for the bytes in front of e: then i >= n)
-            const uint32_t b = (w[k >> 2] >> (8 * (k & 3))) & 0xffu;
-            s += i < n ? (b + 1u) * (i * 0x9e3779b1u + 1u) : 0u;
+        for (int u = 0; u < U; u++) q[u] = v0 + u * nthr < nvec ? base[v0 + u * nthr] : make_uint4(0, 0, 0, 0);
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t v = v0 + u * nthr;
+            const uint32_t w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+#pragma unroll
+            for (uint32_t k = 0; k < 16; k++) {
+                const uint32_t i = 16 * v + k - off;            // (wraps for the bytes in front of e: then i >= n)
+                const uint32_t b = (w[k >> 2] >> (8 * (k & 3))) & 0xffu;
+                s += i < n ? (b + 1u) * (i * 0x9e3779b1u + 1u) : 0u;
+            }
         }
     }
     return s;

@@ -67,11 +67,13 @@ __device__ __forceinline__ void px_load_block(const EncArgs &a, bool valid, uint
 // What a lane knows about its block before any coding decision: per band the sixteen mag-sign deltas in curve order (four
 // to a register), their OR, the value the curve leaves the block with, the value it entered with; the rungs of this block and of
 // the block before it, four bits a band.  Contains ONE workgroup barrier, under which the code table goes to LDS.
+// HALO_LAST: the halo block is the workgroup's LAST lane, not its first (lane 0 of wave 0 then takes the previous block's
+// rungs from it, as the first lane of every other wave takes them from the wave before).
 template <int B> struct PxFront {
     uint32_t gp[B][4], usedv[B], lastv[B], pvv[B];
     uint32_t rp_packed, prp;
 };
-template <int B, bool RGB, uint64_t ORDER>
+template <int B, bool RGB, uint64_t ORDER, bool HALO_LAST = false>
 __device__ __forceinline__ void px_front(const EncArgs &a0, uint32_t gblk, const uint32_t (&w)[4][B], uint32_t pd, uint32_t *etab, uint32_t *wsum,
                                          const uint4 &tabv, PxFront<B> &f) {
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -111,7 +113,7 @@ __device__ __forceinline__ void px_front(const EncArgs &a0, uint32_t gblk, const
     if (lane == 63) wsum[32 + wave] = rp_packed;
     if (tid < 128) ((uint4 *)etab)[tid] = tabv;
     __syncthreads();
-    if (lane == 0 && wave) prp = wsum[32 + wave - 1];
+    if (lane == 0 && (wave || HALO_LAST)) prp = wsum[32 + ((wave + 3) & 3)];
     if (gblk == 0) { prp = 0;
 #pragma unroll
         for (int c = 0; c < B; c++) prp |= ((uint32_t)a0.st.rung[c] & 15u) << (4 * c); }
