@@ -56,6 +56,47 @@ size_t qb3x_encode_device(encsp p, const void *d_src, void *d_dst, void *d_index
  * Returns decoded bytes, 0 on error. */
 size_t qb3x_decode_device(decsp p, const void *d_src, void *d_dst, const void *d_index, void *stream);
 
+/* Window decode: a rectangle of the raster without decoding all of it.  No counterpart in the reference, whose stream has no
+ * restart points (QB3decode.h:445-454); here a container written with qb3x_set_encoder_index_chunk(p, 2) has one per index segment.
+ * Decodes the w x h pixel window whose top-left pixel is (x0, y0) of the raster handle p describes.  d_src, d_index, stream: as
+ * qb3x_decode_device.  d_dst receives h rows of w * bands values; dst_stride is the distance between rows IN VALUES (0: w * bands),
+ * the convention of qb3_set_decoder_stride; the handle's own stride setting is not used by this call.  Returns the bytes of the
+ * window (h * w * bands * value size), 0 on error.
+ * The bytes are, for every container and handle setting (compat flags, quanta, band map, scan order), exactly the crop of what
+ * qb3x_decode_device would write, and the call fails where that call fails, with the same error.  How it gets there
+ * (qb3x_last_window_path):
+ *   1  8-bit rasters of 1, 3 or 4 bands, FTL / BASE, level-2 table in the container, d_index NULL: one kernel decodes the index
+ *      segments that hold a block of the window -- and no others -- straight into d_dst; of the table only the chunks the window's
+ *      entries are read from are checked and read.  Time and memory follow the window, not the raster.
+ *   2  every other raster with a level-2 table (16-bit, 32/64-bit, other band counts, the common-factor modes): the segments of the
+ *      window's block ROWS are decoded into a scratch raster the handle owns, then cropped.  Time follows the window's rows; the
+ *      scratch is raster sized (qb3_decoded_size bytes of device memory).
+ *   3  everything else -- no table or a level-1 one, an out-of-band d_index, the RLE modes, narrow images, STORED containers: the
+ *      whole decode into the scratch raster, then the crop.
+ * Any nonzero status word from path 1 or 2 (a table that fails its check, a segment that does not decode, a stream that ends
+ * early -- seen in the window's segments, or from the table's last entry lying beyond the stream's end) discards what they
+ * wrote and takes path 3: a damaged table costs time, never pixels.  What paths 1 and 2 cannot see is a corrupt unit in a
+ * segment they do not decode: the whole decode fails on such a stream, a window beside the damage does not.
+ * Errors (QB3E_EINV, 0 returned, nothing written): a handle that is not past qb3_read_info, w == 0, h == 0, a window that is not
+ * inside the raster, a nonzero dst_stride below w * bands, d_src not 4-byte aligned.  No byte of d_dst outside the h runs of
+ * w * bands values is written: not the gaps of a wide stride, not behind the last row. */
+size_t qb3x_decode_window_device(decsp p, const void *d_src, const void *d_index, size_t x0, size_t y0, size_t w, size_t h,
+                                 void *d_dst, size_t dst_stride, void *stream);
+/* The same for a container in HOST memory (handle from qb3_read_start + qb3_read_info over the whole container); dst is host
+ * memory.  STORED containers are cropped on the host without a device; otherwise the whole container goes up the link and only
+ * the window comes down. */
+size_t qb3x_read_window(decsp p, size_t x0, size_t y0, size_t w, size_t h, void *dst, size_t dst_stride);
+/* Pure geometry, needs no device: index segments of the raster that hold a block of the window (pixel x is held by block
+ * min(x / 4, blocks per row - 1): the last block column / row is shifted, not padded); *blocks_per_segment (may be NULL) receives
+ * the segment size the count is made with.  0: the window is not inside the raster (or is empty).  STORED containers and narrow
+ * images (a side below 4) have no block grid: every valid window counts 1, *blocks_per_segment is 0. */
+size_t qb3x_window_segments(const decsp p, size_t x0, size_t y0, size_t w, size_t h, size_t *blocks_per_segment);
+/* Diagnostics of the handle's last window call: which way it went (0: none yet or it failed, 1: the window kernel, 2: a strip of
+ * whole block rows + crop, 3: the whole raster + crop) and how many index segments it decoded (path 1: qb3x_window_segments of the
+ * window; 2: those of its block rows; 3: all of the raster's, 0 where there is no block grid). */
+int    qb3x_last_window_path(const decsp p);
+size_t qb3x_last_window_segments(const decsp p);
+
 /* Batched tiles: n images of the encoder's geometry, image i at d_src + i*src_pitch, container i
  * written at d_dst + i*dst_pitch (dst_pitch >= qb3_max_encoded_size, multiple of 4), index i at
  * d_index + i*qb3x_index_size (or NULL).  sizes[i] receives the container size (0 = failed).
@@ -157,7 +198,8 @@ size_t qb3_decode(decsp p, void *destination);                                  
 /* Per-kernel timing for benchmarks: when enabled, every kernel the library launches is bracketed by HIP
  * events on the launch stream; totals are resolved at the library's own synchronisation points.
  * Kernel names: enc_units, enc_scan, enc_concat, enc_seams, enc_best_units, enc_best_scan, enc_best_recode,
- * dec_index_table, dec_index_serial, dec_index_prev, dec_index_scan, dec_units, dec_segments.
+ * dec_index_table, dec_index_serial, dec_index_prev, dec_index_scan, dec_units, dec_segments, dec_window (the window kernel of
+ * qb3x_decode_window_device, path 1).
  * level: 0 off, 1 every kernel, 2 all but the microsecond kernels (enc_scan, enc_seams, enc_best_scan), whose two
  * events cost more than they take. */
 void qb3x_profile_enable(int level);

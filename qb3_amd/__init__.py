@@ -69,6 +69,11 @@ _PROTOS = {
     "qb3x_encode_tiles": (_sz, [_vp, _vp, _sz, _sz, _vp, _sz, _vp, C.POINTER(_sz), _vp]),
     "qb3x_decode_tiles": (_sz, [_vp, _vp, _sz, _sz, C.POINTER(_sz), _vp, _sz, _vp, _vp]),
     "qb3x_decode_tile_ok": (C.c_int, [_vp, _sz]),
+    "qb3x_decode_window_device": (_sz, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp]),
+    "qb3x_read_window": (_sz, [_vp, _sz, _sz, _sz, _sz, _vp, _sz]),
+    "qb3x_window_segments": (_sz, [_vp, _sz, _sz, _sz, _sz, C.POINTER(_sz)]),
+    "qb3x_last_window_path": (C.c_int, [_vp]),
+    "qb3x_last_window_segments": (_sz, [_vp]),
     "qb3x_read_start": (_vp, [_vp, _sz, _sz, C.POINTER(_sz)]),
     "qb3x_read_start_device": (_vp, [_vp, _sz, C.POINTER(_sz), _vp]),
     "qb3x_header_size_bound": (_sz, [_vp, _sz]),
@@ -156,5 +161,31 @@ def decode(stream, compat=0):
         if n == 0:
             raise RuntimeError(f"qb3_read_data failed: {last_error()}")
         return out[:n], tuple(dims), lib.qb3_get_type(p), lib.qb3_get_mode(p)
+    finally:
+        lib.qb3_destroy_decoder(p)
+
+
+NP_DTYPE = ("uint8", "int8", "uint16", "int16", "uint32", "int32", "uint64", "int64")      # numpy / torch names of the qb3_dtype codes
+
+
+def decode_window(stream, x0, y0, w, h, compat=0):
+    """qb3_read_start .. qb3x_read_window: the w x h window at (x0, y0) of a container in host memory, as an array of shape
+    (h, w, bands) and the raster's type."""
+    import numpy as np
+    buf = np.ascontiguousarray(stream, dtype=np.uint8)
+    dims = (_sz * 3)()
+    p = lib.qb3_read_start(_np_ptr(buf), buf.size, dims)
+    if not p:
+        raise ValueError("qb3_read_start rejected the stream")
+    try:
+        if not lib.qb3_read_info(p):
+            raise ValueError("qb3_read_info failed")
+        if compat:
+            lib.qb3x_set_decoder_compat(p, compat)
+        out = np.empty((h, w, dims[2]), dtype=NP_DTYPE[lib.qb3_get_type(p)])
+        n = lib.qb3x_read_window(p, x0, y0, w, h, _np_ptr(out), 0)
+        if n == 0:
+            raise RuntimeError(f"qb3x_read_window failed: {last_error()}")
+        return out
     finally:
         lib.qb3_destroy_decoder(p)

@@ -292,6 +292,9 @@ struct decs {
     std::vector<uint8_t> tile_ok;   // qb3x_decode_tiles: per tile outcome of the last call
     uint32_t last_status = 0;       // status bits of the last decode call (qb3x_last_decode_status; tiles: of all tiles together)
     DevBuf d_in, d_img, d_ws, d_ix, d_rle, d_tab;      // d_rle: RLE0 workspace (+ the packed bytes of a host call); d_tab: the unit-length table a plain 8-bit stream is walked through
+    DevBuf d_win, d_wst, d_wout, d_wsrc;               // window calls: the raster a strip or a whole decode goes to before the crop; the window kernel's status word; a host call's window and container
+    int win_path = 0;                                  // ... which way the last one went (qb3x_last_window_path) and how many segments it decoded
+    size_t win_segs = 0;
     Stager stager, stager2;                            // (stager2: the download ring of a pipelined host call)
     Pipe pipe;                                         // ... its streams and events
 };
@@ -924,7 +927,7 @@ static size_t encode_tiles_body(encsp p, const void *d_src, size_t n, size_t src
 // ---------------------------------------------------------------- decoder handle
 QB3_API void qb3_destroy_decoder(decsp p) {
     if (!p) return;
-    release_all(p->d_in, p->d_img, p->d_ws, p->d_ix, p->d_rle, p->d_tab);
+    release_all(p->d_in, p->d_img, p->d_ws, p->d_ix, p->d_rle, p->d_tab, p->d_win, p->d_wst, p->d_wout, p->d_wsrc);
     p->stager.release(); p->stager2.release(); p->pipe.release();
     delete p;
 }
@@ -1503,6 +1506,167 @@ QB3_API size_t qb3x_decode_device(decsp p, const void *d_src, void *d_dst, const
     if (!p || !d_src || !d_dst || ((uintptr_t)d_src & 3)) { if (p) p->error = QB3E_EINV; return 0; }
     return abi_guard<size_t>(0, [&] { return decode_common(p, nullptr, d_src, d_dst, d_index, (hipStream_t)stream); });
 }
+
+// ---------------------------------------------------------------- window decode
+// A rectangle of the raster.  The definition is "decode everything, crop" (path 3); the other two ways are shortcuts to the same
+// bytes that are taken when the container carries a level-2 table and dropped again on ANY nonzero status word:
+//   path 1  8-bit rasters of 1, 3 or 4 bands, FTL / BASE: the window kernel (k_dec_win.hip) decodes only the segments that hold a
+//           block of the window, straight into the caller's buffer;
+//   path 2  every other raster that decodes strip by strip (decode_strips_ok): one strip of the window's block rows into the
+//           handle's scratch raster, then the crop;
+//   path 3  the whole decode with its fallback ladder into the scratch raster, then the crop.
+struct WinCall { size_t x0, y0, w, h, stride; };        // stride: values between the destination's rows (never 0 here)
+
+// the geometry decode_common decodes a coded, not narrow raster with (rows tight)
+static Geometry decoder_geometry(const decs *p) {
+    uint8_t cband[QB3_MAXBANDS];
+    for (size_t c = 0; c < QB3_MAXBANDS; c++) cband[c] = p->cband[c];
+    if (!p->saw_cb && !(p->compat & QB3X_REF_CBAND0)) for (size_t c = 0; c < p->nbands; c++) cband[c] = (uint8_t)c;
+    return make_geometry(p->xsize, p->ysize, p->nbands, p->type, 0, p->order, p->mode, nullptr, cband);
+}
+
+// handle and rectangle of a window call; false: p->error is set, nothing was touched
+static bool window_check(decsp p, size_t x0, size_t y0, size_t w, size_t h, size_t dst_stride) {
+    if (p->stage != 2 || p->error != QB3E_OK || p->s_in == nullptr || p->s_size == 0) {
+        if (p->error == QB3E_OK) p->error = QB3E_EINV;
+        return false;
+    }
+    if (!w || !h || x0 >= p->xsize || w > p->xsize - x0 || y0 >= p->ysize || h > p->ysize - y0 || (dst_stride && dst_stride < w * p->nbands)) {
+        p->error = QB3E_EINV;
+        return false;
+    }
+    return true;
+}
+
+// rows [y0, y0 + h) x columns [x0, x0 + w) of a tight raster in device memory into the window's buffer (device or host)
+static bool window_crop(decsp p, const void *d_raster, const WinCall &wc, void *dst, hipMemcpyKind kind, hipStream_t st) {
+    const size_t pix = p->nbands * szof(p->type), line = p->xsize * pix;
+    hipError_t e = hipMemcpy2DAsync(dst, wc.stride * szof(p->type), (const uint8_t *)d_raster + wc.y0 * line + wc.x0 * pix, line, wc.w * pix, wc.h, kind, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);      // (the scratch raster is the handle's: the next call may come on another stream)
+    if (e != hipSuccess) { set_error("window crop", (int)e); p->error = QB3E_LIBERR; return false; }
+    return true;
+}
+
+static size_t window_device(decsp p, const void *d_src, const void *d_index, const WinCall &wc, void *d_dst, hipStream_t st) {
+    const size_t tsz = szof(p->type), pix = p->nbands * tsz, total = qb3_decoded_size(p), wbytes = wc.h * wc.w * pix;
+    const bool coded = p->mode != QB3M_STORED && p->xsize >= 4 && p->ysize >= 4;       // (narrow images decode through a stand-in shape: no block grid)
+    p->win_path = 0; p->win_segs = 0;
+    Geometry g;
+    memset(&g, 0, sizeof(g));
+    if (coded) g = decoder_geometry(p);
+    if (coded && !d_index && p->ix_K && p->ix_bl && !is_rle_mode(p->mode)) {
+        if (!device_ok()) { p->error = QB3E_LIBERR; return 0; }
+        const DecPlan plan = plan_decode(g);
+        IxTable ixt;
+        ixt.K = p->ix_K; ixt.blocks = p->ix_blocks; ixt.entry_bytes = p->ix_E; ixt.per_chunk = p->ix_per_chunk; ixt.pads = p->ix_pads; ixt.block_lens = p->ix_bl;
+        ixt.version = p->ix_ver; ixt.check_heads = p->ix_heads_unchecked;
+        ixt.base = (uint8_t *)d_src + p->ix_off;
+        const size_t off = (size_t)(p->s_in - p->s_start);
+        const uint32_t *in32 = (const uint32_t *)((const uint8_t *)d_src + (off & ~(size_t)3));
+        const uint32_t in_bit0 = (uint32_t)(8 * (off & 3));
+        const WinRect r = { (uint32_t)wc.x0, (uint32_t)wc.y0, (uint32_t)wc.w, (uint32_t)wc.h, wc.stride };
+        Geometry gw = g;                                    // the window as a raster of its own: what is dequantised
+        gw.w = r.w; gw.h = r.h; gw.stride = wc.stride;
+        uint32_t status = 1;
+        int path = 0;
+        size_t segs = 0;
+        if (decode_window_ok(g, plan, ixt)) {
+            if (!p->d_wst.ensure(64)) { p->error = QB3E_LIBERR; return 0; }
+            if (launch_decode_window(g, plan, in32, in_bit0, (uint64_t)p->s_size * 8, d_dst, r, (uint32_t *)p->d_wst.p, st, ixt)) { p->error = QB3E_LIBERR; return 0; }
+            const hipError_t e = fetch_small(&status, p->d_wst.p, 4, st);
+            if (e != hipSuccess) { set_error("window kernel", (int)e); p->error = QB3E_LIBERR; return 0; }
+            path = 1; segs = (size_t)window_segments(g, r);
+        } else if (decode_strips_ok(g, plan, ixt)) {
+            // the segments of the window's block rows, first-strip semantics (status zeroed, table checked), into the scratch raster
+            if (!p->d_win.ensure(total) || !p->d_ws.ensure(plan.ws_bytes)) { p->error = QB3E_LIBERR; return 0; }
+            const uint64_t by0 = std::min<uint64_t>(wc.y0 / 4, g.nby - 1), by1 = std::min<uint64_t>((wc.y0 + wc.h - 1) / 4, g.nby - 1);
+            const uint64_t seg0 = by0 * g.nbx / g.seg_blocks, seg1 = ((by1 + 1) * g.nbx - 1) / g.seg_blocks + 1;
+            const DecStrip strip = { seg0, seg1 - seg0, true };
+            uint32_t *d_status = nullptr;
+            if (launch_decode(g, plan, in32, in_bit0, (uint64_t)p->s_size * 8, p->d_win.p, nullptr, p->d_ws.p, &d_status, st, TileBatch(), nullptr, ixt,
+                              nullptr, 0, false, 16, &strip)) { p->error = QB3E_LIBERR; return 0; }
+            if (launch_window_tail_check(g, (uint64_t)p->s_size * 8, d_status, st, ixt)) { p->error = QB3E_LIBERR; return 0; }
+            const hipError_t e = fetch_small(&status, d_status, 4, st);
+            if (e != hipSuccess) { set_error("window strip", (int)e); p->error = QB3E_LIBERR; return 0; }
+            if (!status && !window_crop(p, p->d_win.p, wc, d_dst, hipMemcpyDeviceToDevice, st)) return 0;
+            path = 2; segs = (size_t)(seg1 - seg0);
+        }
+        prof_collect();
+        if (path && !status) {
+            p->last_status = 0;
+            if (p->quanta > 1 && launch_dequantize(d_dst, gw, (int)p->type, p->quanta, st)) { p->error = QB3E_LIBERR; return 0; }
+            p->win_path = path; p->win_segs = segs;
+            return wbytes;
+        }
+        // a table that failed its check, a segment that did not decode, a stream that ends early: what the shortcut wrote is
+        // overwritten below by the crop of the whole decode
+    }
+    if (!p->d_win.ensure(total)) { p->error = QB3E_LIBERR; return 0; }
+    const size_t keep = p->stride;
+    p->stride = 0;                                          // (the scratch raster is tight; the caller's setting is for qb3_read_data)
+    const size_t n = decode_common(p, nullptr, d_src, p->d_win.p, d_index, st);
+    p->stride = keep;
+    if (!n) return 0;
+    if (!window_crop(p, p->d_win.p, wc, d_dst, hipMemcpyDeviceToDevice, st)) return 0;
+    p->win_path = 3; p->win_segs = coded ? (size_t)g.nseg : 0;
+    return wbytes;
+}
+
+QB3_API size_t qb3x_decode_window_device(decsp p, const void *d_src, const void *d_index, size_t x0, size_t y0, size_t w, size_t h,
+                                         void *d_dst, size_t dst_stride, void *stream) {
+    if (!p || !d_src || !d_dst || ((uintptr_t)d_src & 3)) { if (p) p->error = QB3E_EINV; return 0; }
+    return abi_guard<size_t>(0, [&]() -> size_t {
+        if (!window_check(p, x0, y0, w, h, dst_stride)) return 0;
+        const WinCall wc = { x0, y0, w, h, dst_stride ? dst_stride : w * p->nbands };
+        return window_device(p, d_src, d_index, wc, d_dst, (hipStream_t)stream);
+    });
+}
+
+QB3_API size_t qb3x_read_window(decsp p, size_t x0, size_t y0, size_t w, size_t h, void *dst, size_t dst_stride) {
+    if (!p || !dst) { if (p) p->error = QB3E_EINV; return 0; }
+    return abi_guard<size_t>(0, [&]() -> size_t {
+        if (!window_check(p, x0, y0, w, h, dst_stride)) return 0;
+        const size_t tsz = szof(p->type), pix = p->nbands * tsz, line = p->xsize * pix, wline = w * pix, wbytes = h * wline;
+        const size_t stride = dst_stride ? dst_stride : w * p->nbands, data_off = (size_t)(p->s_in - p->s_start), csize = data_off + p->s_size;
+        if (p->hdr_avail < csize) { p->error = QB3E_EINV; return 0; }        // (a handle over a copy of the container's head only: as qb3_read_data)
+        p->win_path = 0; p->win_segs = 0;
+        if (p->mode == QB3M_STORED) {           // raw pixels: cropped on the host, no device needed (reference QB3decode.cpp:356-375)
+            if (p->s_size != qb3_decoded_size(p)) { p->error = QB3E_EINV; return 0; }
+            for (size_t y = 0; y < h; y++) memcpy((uint8_t *)dst + y * stride * tsz, p->s_in + (y0 + y) * line + x0 * pix, wline);
+            p->win_path = 3;
+            return wbytes;
+        }
+        if (p->xsize * p->ysize < 16) { p->error = QB3E_EINV; return 0; }
+        if (!device_ok()) { p->error = QB3E_LIBERR; return 0; }
+        // the whole container goes up (the stream and its table), the window alone comes down
+        hipStream_t st = nullptr;
+        if (!p->d_wsrc.ensure(csize + 8) || !p->d_wout.ensure(wbytes)) { p->error = QB3E_LIBERR; return 0; }
+        if (!upload(p->stager, p->d_wsrc.p, p->s_start, csize, st)) { p->error = QB3E_LIBERR; return 0; }
+        HIPOK(hipMemsetAsync((uint8_t *)p->d_wsrc.p + csize, 0, 8, st));      // (a stream that ends early reads as zeros behind its end)
+        const WinCall wc = { x0, y0, w, h, w * p->nbands };
+        if (!window_device(p, p->d_wsrc.p, nullptr, wc, p->d_wout.p, st)) return 0;
+        if (stride * tsz == wline) { if (!download(p->stager, dst, p->d_wout.p, wbytes, st)) { p->error = QB3E_LIBERR; return 0; } }
+        else {
+            HIPOK(hipMemcpy2DAsync(dst, stride * tsz, p->d_wout.p, wline, wline, h, hipMemcpyDeviceToHost, st));
+            HIPOK(hipStreamSynchronize(st));
+        }
+        return wbytes;
+    });
+}
+
+QB3_API size_t qb3x_window_segments(const decsp p, size_t x0, size_t y0, size_t w, size_t h, size_t *blocks_per_segment) {
+    if (blocks_per_segment) *blocks_per_segment = 0;
+    if (!p || p->stage != 2 || !w || !h || x0 >= p->xsize || w > p->xsize - x0 || y0 >= p->ysize || h > p->ysize - y0) return 0;
+    if (p->mode == QB3M_STORED || p->xsize < 4 || p->ysize < 4) return 1;      // no block grid: one piece
+    return abi_guard<size_t>(0, [&]() -> size_t {
+        const Geometry g = decoder_geometry(p);
+        if (blocks_per_segment) *blocks_per_segment = g.seg_blocks;
+        const WinRect r = { (uint32_t)x0, (uint32_t)y0, (uint32_t)w, (uint32_t)h, 0 };
+        return (size_t)window_segments(g, r);
+    });
+}
+QB3_API int qb3x_last_window_path(const decsp p) { return p ? p->win_path : 0; }
+QB3_API size_t qb3x_last_window_segments(const decsp p) { return p ? p->win_segs : 0; }
 
 // One tile through its own header: a host copy of its head is parsed into a handle of its own (a batch may hold
 // containers of another kind than tile 0's: raw-stored tiles next to coded ones, QB3encode.cpp:571-573)

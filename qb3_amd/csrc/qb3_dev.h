@@ -240,6 +240,22 @@ int launch_decode(const Geometry &g, const DecPlan &plan, const uint32_t *in32, 
 // lane-per-block decoder per range of segments, nothing else
 bool decode_strips_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix);
 
+// Window decode (k_dec_win.hip): a rectangle of the raster from the container's level-2 table, only the index segments that hold one
+// of its blocks.  x0, y0, w, h in raster pixels; stride: values between the rows of the destination, which receives the window alone.
+struct WinRect { uint32_t x0, y0, w, h; uint64_t stride; };
+// index segments of the raster that hold a block of the window (pure geometry: needs w, h, nbx, nby, seg_blocks; 0: the window is
+// empty or not inside the raster).  Pixel x is held by block min(x / 4, nbx - 1): the last block column / row is shifted, not padded.
+uint64_t window_segments(const Geometry &g, const WinRect &r);
+// does the window kernel take this raster and table: what dec_px_kernel decodes from the entries alone (8-bit, 1/3/4 bands, FTL / BASE)
+bool decode_window_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix);
+// One launch (its first workgroups check the table chunks the window's entries are read from); status: a device word of the caller's,
+// zeroed here -- nonzero afterwards means "do not trust the window's bytes".  Does not synchronise.  Returns hipError_t as int.
+int launch_decode_window(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
+                         void *dst, const WinRect &r, uint32_t *status, void *stream, const IxTable &ix);
+// behind a strip of launch_decode (which has checked the table): status bit 2 when the table's last entry lies beyond the stream's end
+// -- a stream cut short, which only the whole decode may judge
+int launch_window_tail_check(const Geometry &g, uint64_t in_bits, uint32_t *status, void *stream, const IxTable &ix);
+
 // The RLE0 byte pass of the *_RLE modes on device buffers (k_rle0.hip; reference QB3encode.cpp:271-332, QB3decode.cpp:267-307).
 // ws: rle0_ws_bytes(n) bytes of device memory.  rle0_device_size returns the size of the coded (decode = false) or
 // expanded (decode = true) form and synchronises the stream; rle0_device_write, called next with the same arguments,

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import lib, last_error, TYPESIZE, QB3M_FTL, _sz
+from . import lib, last_error, TYPESIZE, NP_DTYPE, QB3M_FTL, _sz
 
 _vp = C.c_void_p
 
@@ -107,6 +107,26 @@ class DeviceDecoder:
         if n == 0:
             raise RuntimeError(f"qb3x_decode_device failed: {last_error()}")
         return out
+
+    def decode_window(self, d_stream, x0, y0, w, h, out=None, index=None):
+        """the w x h window at (x0, y0) of the raster (qb3x_decode_window_device): a device tensor of shape (h, w, bands) and the
+        raster's type.  out: a contiguous uint8 device tensor of at least the window's bytes to decode into."""
+        assert d_stream.is_cuda
+        dt = lib.qb3_get_type(self.p)
+        nbytes = h * w * self.bands * TYPESIZE[dt]
+        if out is None:
+            out = torch.empty(nbytes, dtype=torch.uint8, device=d_stream.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8 and out.numel() >= nbytes
+        n = lib.qb3x_decode_window_device(self.p, _vp(d_stream.data_ptr()), _vp(index.data_ptr()) if index is not None else None,
+                                          x0, y0, w, h, _vp(out.data_ptr()), 0, _stream_ptr())
+        if n == 0:
+            raise RuntimeError(f"qb3x_decode_window_device failed: {last_error()}")
+        return out.view(-1)[:nbytes].view(getattr(torch, NP_DTYPE[dt])).view(h, w, self.bands)
+
+    @property
+    def last_window(self):
+        """(path, segments) of the last decode_window: 1 the window kernel, 2 a strip of block rows + crop, 3 the whole raster + crop"""
+        return lib.qb3x_last_window_path(self.p), lib.qb3x_last_window_segments(self.p)
 
 
 class TileBatchCoder:
