@@ -97,6 +97,39 @@ size_t qb3x_window_segments(const decsp p, size_t x0, size_t y0, size_t w, size_
 int    qb3x_last_window_path(const decsp p);
 size_t qb3x_last_window_segments(const decsp p);
 
+/* A batch of windows: n rectangles of ONE raster in one call -- what a tile server, a viewer or a cropping loader asks of a raster
+ * it keeps in device memory.  wins is a HOST array; dst is a device pointer for qb3x_decode_windows_device and a host pointer for
+ * qb3x_read_windows; dst_stride is in values, 0 meaning w * bands.  Both return the number of windows written.
+ * Bytes: for every i, what qb3x_decode_window_device(p, d_src, d_index, x0, y0, w, h, dst, dst_stride, stream) writes -- the crop
+ * of the whole decode, for every container and handle setting -- and no byte outside the window's h runs of w * bands values.
+ * Destinations may lie in one buffer (a mosaic, an atlas); they must not overlap, which is the caller's duty and is not checked.
+ * Errors are decided before anything is launched or written (QB3E_EINV, 0 returned): a handle that is not past qb3_read_info,
+ * wins == NULL, n == 0, n > 2^20, d_src not 4-byte aligned, and ANY window the single call would refuse (empty, not inside the
+ * raster, a nonzero stride below w * bands, dst == NULL): one bad window refuses the whole batch.
+ * What the batch saves over n single calls:
+ *   path 1  ONE kernel launch decodes every window: a descriptor per window goes up in one copy, a wave finds its window by a
+ *           search over the windows' wave counts, a status word per window comes back in one copy.  A table chunk is checked once
+ *           a call, however many windows read entries from it.
+ *   path 2  the windows' ranges of block rows are merged; every merged range is one launch into the scratch raster, a segment is
+ *           decoded at most once a call; then one status word, and a crop per window.
+ *   path 3  ONE whole decode a call, at most: all windows that end on path 3 share it and are cropped from the scratch raster.
+ * A damaged table costs time, never pixels, window by window: on path 1 a window whose segments raise a nonzero status gets the
+ * crop of the whole decode, the other windows keep what the kernel wrote.  A table chunk that fails its check, or a table whose
+ * last entry lies beyond the stream's end, sends every window to the whole decode; so does a nonzero status on path 2.
+ * Afterwards qb3x_window_ok / qb3x_window_path tell how window i went, qb3x_last_window_path is the path of the batch's last
+ * window, and qb3x_last_window_segments counts the segments the call's kernels decoded in total: on path 1 a segment two windows
+ * share counts twice; where a whole decode ran the raster's count is added once.  With quanta above 1 every window is
+ * dequantised as a raster of its own, as in the single call.  The call synchronises `stream` once on the good path, to read the
+ * status words. */
+typedef struct { size_t x0, y0, w, h; void *dst; size_t dst_stride; } qb3x_window;
+size_t qb3x_decode_windows_device(decsp p, const void *d_src, const void *d_index, const qb3x_window *wins, size_t n, void *stream);
+/* The same for a container in HOST memory and host destinations: the container goes up ONCE, the windows are decoded into one device
+ * buffer and come down one by one.  STORED containers are cropped on the host without a device.  A handle over the container's head
+ * only is refused (QB3E_EINV), as by qb3x_read_window. */
+size_t qb3x_read_windows(decsp p, const qb3x_window *wins, size_t n);
+int    qb3x_window_ok(const decsp p, size_t i);     /* 1: window i of the last batch call was written */
+int    qb3x_window_path(const decsp p, size_t i);   /* 0 failed, 1 / 2 / 3 as qb3x_last_window_path */
+
 /* Batched tiles: n images of the encoder's geometry, image i at d_src + i*src_pitch, container i
  * written at d_dst + i*dst_pitch (dst_pitch >= qb3_max_encoded_size, multiple of 4), index i at
  * d_index + i*qb3x_index_size (or NULL).  sizes[i] receives the container size (0 = failed).

@@ -34,6 +34,21 @@ QB3X_REF_CBAND0 = 1
 TYPESIZE = (1, 1, 2, 2, 4, 4, 8, 8)
 
 _vp, _sz, _u64 = C.c_void_p, C.c_size_t, C.c_uint64
+
+
+class Window(C.Structure):
+    """qb3x_window (include/qb3x.h): a rectangle of the raster and where its pixels go; dst_stride in values, 0: w * bands"""
+    _fields_ = [("x0", _sz), ("y0", _sz), ("w", _sz), ("h", _sz), ("dst", _vp), ("dst_stride", _sz)]
+
+
+def window_array(rects, ptrs, strides=None):
+    """a qb3x_window array from (x0, y0, w, h) tuples, destination addresses and (optional) strides in values"""
+    arr = (Window * len(rects))()
+    for i, (x0, y0, w, h) in enumerate(rects):
+        arr[i] = Window(x0, y0, w, h, ptrs[i], strides[i] if strides else 0)
+    return arr
+
+
 _PROTOS = {
     # name: (restype, argtypes)            -- include/QB3.h
     "qb3_create_encoder": (_vp, [_sz, _sz, _sz, C.c_int]),
@@ -74,6 +89,10 @@ _PROTOS = {
     "qb3x_window_segments": (_sz, [_vp, _sz, _sz, _sz, _sz, C.POINTER(_sz)]),
     "qb3x_last_window_path": (C.c_int, [_vp]),
     "qb3x_last_window_segments": (_sz, [_vp]),
+    "qb3x_decode_windows_device": (_sz, [_vp, _vp, _vp, _vp, _sz, _vp]),
+    "qb3x_read_windows": (_sz, [_vp, _vp, _sz]),
+    "qb3x_window_ok": (C.c_int, [_vp, _sz]),
+    "qb3x_window_path": (C.c_int, [_vp, _sz]),
     "qb3x_read_start": (_vp, [_vp, _sz, _sz, C.POINTER(_sz)]),
     "qb3x_read_start_device": (_vp, [_vp, _sz, C.POINTER(_sz), _vp]),
     "qb3x_header_size_bound": (_sz, [_vp, _sz]),
@@ -187,5 +206,30 @@ def decode_window(stream, x0, y0, w, h, compat=0):
         if n == 0:
             raise RuntimeError(f"qb3x_read_window failed: {last_error()}")
         return out
+    finally:
+        lib.qb3_destroy_decoder(p)
+
+
+def decode_windows(stream, rects, compat=0):
+    """qb3_read_start .. qb3x_read_windows: the windows (x0, y0, w, h) of `rects` of a container in host memory -- one upload, one
+    decode call -- as a list of arrays of shape (h, w, bands) and the raster's type."""
+    import numpy as np
+    buf = np.ascontiguousarray(stream, dtype=np.uint8)
+    dims = (_sz * 3)()
+    p = lib.qb3_read_start(_np_ptr(buf), buf.size, dims)
+    if not p:
+        raise ValueError("qb3_read_start rejected the stream")
+    try:
+        if not lib.qb3_read_info(p):
+            raise ValueError("qb3_read_info failed")
+        if compat:
+            lib.qb3x_set_decoder_compat(p, compat)
+        rects = [tuple(int(v) for v in r) for r in rects]
+        outs = [np.empty((h, w, dims[2]), dtype=NP_DTYPE[lib.qb3_get_type(p)]) for _, _, w, h in rects]
+        wins = window_array(rects, [o.ctypes.data for o in outs])
+        n = lib.qb3x_read_windows(p, wins, len(rects))
+        if n != len(rects):
+            raise RuntimeError(f"qb3x_read_windows wrote {n} of {len(rects)} windows: {last_error()}")
+        return outs
     finally:
         lib.qb3_destroy_decoder(p)

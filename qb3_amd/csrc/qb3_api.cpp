@@ -107,6 +107,20 @@ struct DevBuf {
         p = nullptr; cap = 0;
     }
 };
+// a small pinned host area a handle owns (descriptors up, status words back: one copy each way, no staging by the runtime)
+struct PinBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    bool ensure(size_t n) {
+        if (n <= cap) return true;
+        release();
+        n = std::max<size_t>(n + n / 2, 4096);
+        if (hipHostMalloc(&p, n, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); set_error("hipHostMalloc", 0); p = nullptr; return false; }
+        cap = n;
+        return true;
+    }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+};
 template <class... B> static void release_all(B &...b) {
     bool any = false;
     for (bool h : {(b.p != nullptr)...}) any = any || h;
@@ -295,6 +309,9 @@ struct decs {
     DevBuf d_win, d_wst, d_wout, d_wsrc;               // window calls: the raster a strip or a whole decode goes to before the crop; the window kernel's status word; a host call's window and container
     int win_path = 0;                                  // ... which way the last one went (qb3x_last_window_path) and how many segments it decoded
     size_t win_segs = 0;
+    DevBuf d_wdesc;                                    // a batch of windows: descriptors and the list of table chunks to check, as uploaded
+    PinBuf h_wdesc, h_wst;                             // ... their pinned host copy (one copy up), and the status words (one copy back)
+    std::vector<uint8_t> wins_path;                    // ... per window outcome of the last batch call (0: not written, else its path)
     Stager stager, stager2;                            // (stager2: the download ring of a pipelined host call)
     Pipe pipe;                                         // ... its streams and events
 };
@@ -927,7 +944,8 @@ static size_t encode_tiles_body(encsp p, const void *d_src, size_t n, size_t src
 // ---------------------------------------------------------------- decoder handle
 QB3_API void qb3_destroy_decoder(decsp p) {
     if (!p) return;
-    release_all(p->d_in, p->d_img, p->d_ws, p->d_ix, p->d_rle, p->d_tab, p->d_win, p->d_wst, p->d_wout, p->d_wsrc);
+    release_all(p->d_in, p->d_img, p->d_ws, p->d_ix, p->d_rle, p->d_tab, p->d_win, p->d_wst, p->d_wout, p->d_wsrc, p->d_wdesc);
+    p->h_wdesc.release(); p->h_wst.release();
     p->stager.release(); p->stager2.release(); p->pipe.release();
     delete p;
 }
@@ -1539,12 +1557,22 @@ static bool window_check(decsp p, size_t x0, size_t y0, size_t w, size_t h, size
 }
 
 // rows [y0, y0 + h) x columns [x0, x0 + w) of a tight raster in device memory into the window's buffer (device or host)
-static bool window_crop(decsp p, const void *d_raster, const WinCall &wc, void *dst, hipMemcpyKind kind, hipStream_t st) {
+static bool window_crop(decsp p, const void *d_raster, const WinCall &wc, void *dst, hipMemcpyKind kind, hipStream_t st, bool wait = true) {
     const size_t pix = p->nbands * szof(p->type), line = p->xsize * pix;
     hipError_t e = hipMemcpy2DAsync(dst, wc.stride * szof(p->type), (const uint8_t *)d_raster + wc.y0 * line + wc.x0 * pix, line, wc.w * pix, wc.h, kind, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);      // (the scratch raster is the handle's: the next call may come on another stream)
+    if (e == hipSuccess && wait) e = hipStreamSynchronize(st);      // (the scratch raster is the handle's: the next call may come on another stream)
     if (e != hipSuccess) { set_error("window crop", (int)e); p->error = QB3E_LIBERR; return false; }
     return true;
+}
+
+// the container's table and the stream's first bit, as the kernels take them, of a container in device memory
+static void window_source(const decs *p, const void *d_src, IxTable *ixt, const uint32_t **in32, uint32_t *in_bit0) {
+    ixt->K = p->ix_K; ixt->blocks = p->ix_blocks; ixt->entry_bytes = p->ix_E; ixt->per_chunk = p->ix_per_chunk; ixt->pads = p->ix_pads; ixt->block_lens = p->ix_bl;
+    ixt->version = p->ix_ver; ixt->check_heads = p->ix_heads_unchecked;
+    ixt->base = (uint8_t *)d_src + p->ix_off;
+    const size_t off = (size_t)(p->s_in - p->s_start);
+    *in32 = (const uint32_t *)((const uint8_t *)d_src + (off & ~(size_t)3));
+    *in_bit0 = (uint32_t)(8 * (off & 3));
 }
 
 static size_t window_device(decsp p, const void *d_src, const void *d_index, const WinCall &wc, void *d_dst, hipStream_t st) {
@@ -1558,12 +1586,9 @@ static size_t window_device(decsp p, const void *d_src, const void *d_index, con
         if (!device_ok()) { p->error = QB3E_LIBERR; return 0; }
         const DecPlan plan = plan_decode(g);
         IxTable ixt;
-        ixt.K = p->ix_K; ixt.blocks = p->ix_blocks; ixt.entry_bytes = p->ix_E; ixt.per_chunk = p->ix_per_chunk; ixt.pads = p->ix_pads; ixt.block_lens = p->ix_bl;
-        ixt.version = p->ix_ver; ixt.check_heads = p->ix_heads_unchecked;
-        ixt.base = (uint8_t *)d_src + p->ix_off;
-        const size_t off = (size_t)(p->s_in - p->s_start);
-        const uint32_t *in32 = (const uint32_t *)((const uint8_t *)d_src + (off & ~(size_t)3));
-        const uint32_t in_bit0 = (uint32_t)(8 * (off & 3));
+        const uint32_t *in32;
+        uint32_t in_bit0;
+        window_source(p, d_src, &ixt, &in32, &in_bit0);
         const WinRect r = { (uint32_t)wc.x0, (uint32_t)wc.y0, (uint32_t)wc.w, (uint32_t)wc.h, wc.stride };
         Geometry gw = g;                                    // the window as a raster of its own: what is dequantised
         gw.w = r.w; gw.h = r.h; gw.stride = wc.stride;
@@ -1653,6 +1678,197 @@ QB3_API size_t qb3x_read_window(decsp p, size_t x0, size_t y0, size_t w, size_t 
         return wbytes;
     });
 }
+
+// ---------------------------------------------------------------- a batch of windows
+// Many rectangles of one raster in one call.  Every window's bytes are those of the single call; what the batch saves is what the
+// single call pays per window: on path 1 ONE launch decodes all windows and one copy brings a status word per window back; on
+// path 2 the windows' ranges of block rows are merged and a segment is decoded once; all windows that end on path 3 share ONE
+// whole decode.
+static bool windows_check(decsp p, const qb3x_window *wins, size_t n) {
+    if (p->stage != 2 || p->error != QB3E_OK || p->s_in == nullptr || p->s_size == 0) {
+        if (p->error == QB3E_OK) p->error = QB3E_EINV;
+        return false;
+    }
+    if (!wins || !n || n > ((size_t)1 << 20)) { p->error = QB3E_EINV; return false; }
+    for (size_t i = 0; i < n; i++) {
+        if (!wins[i].dst) { p->error = QB3E_EINV; return false; }
+        if (!window_check(p, wins[i].x0, wins[i].y0, wins[i].w, wins[i].h, wins[i].dst_stride)) return false;
+    }
+    return true;
+}
+
+static size_t windows_device(decsp p, const void *d_src, const void *d_index, const qb3x_window *wins, size_t n, hipStream_t st) {
+    const size_t total = qb3_decoded_size(p);
+    const bool coded = p->mode != QB3M_STORED && p->xsize >= 4 && p->ysize >= 4;       // (narrow images decode through a stand-in shape: no block grid)
+    p->win_path = 0; p->win_segs = 0;
+    p->wins_path.assign(n, 0);
+    auto call_of = [&](size_t i) { return WinCall{ wins[i].x0, wins[i].y0, wins[i].w, wins[i].h, wins[i].dst_stride ? wins[i].dst_stride : wins[i].w * p->nbands }; };
+    Geometry g;
+    memset(&g, 0, sizeof(g));
+    if (coded) g = decoder_geometry(p);
+    auto dequantize = [&](size_t i) {                       // the window as a raster of its own
+        const WinCall wc = call_of(i);
+        Geometry gw = g;
+        gw.w = (uint32_t)wc.w; gw.h = (uint32_t)wc.h; gw.stride = wc.stride;
+        return p->quanta <= 1 || !launch_dequantize(wins[i].dst, gw, (int)p->type, p->quanta, st);
+    };
+    auto fail = [&]() -> size_t { (void)hipStreamSynchronize(st); p->error = QB3E_LIBERR; return 0; };    // (nothing of the handle's stays in flight)
+    size_t segs = 0, todo = n;                              // todo: windows that have no pixels yet
+    if (coded && !d_index && p->ix_K && p->ix_bl && !is_rle_mode(p->mode)) {
+        if (!device_ok()) { p->error = QB3E_LIBERR; return 0; }
+        const DecPlan plan = plan_decode(g);
+        IxTable ixt;
+        const uint32_t *in32;
+        uint32_t in_bit0;
+        window_source(p, d_src, &ixt, &in32, &in_bit0);
+        if (decode_window_ok(g, plan, ixt)) {
+            // descriptors and the chunk list: built in the pinned area, one copy up; n + 1 status words, one memset, one copy back
+            const size_t dbytes = n * WIN_DESC_BYTES, upbytes = dbytes + 4 * ix_chunks(ixt), stbytes = 4 * (n + 1);
+            if (!p->h_wdesc.ensure(upbytes) || !p->h_wst.ensure(stbytes) || !p->d_wdesc.ensure(upbytes) || !p->d_wst.ensure(stbytes)) { p->error = QB3E_LIBERR; return 0; }
+            std::vector<WinRect> rects(n);
+            std::vector<void *> dsts(n);
+            for (size_t i = 0; i < n; i++) {
+                const WinCall wc = call_of(i);
+                rects[i] = WinRect{ (uint32_t)wc.x0, (uint32_t)wc.y0, (uint32_t)wc.w, (uint32_t)wc.h, wc.stride };
+                dsts[i] = wins[i].dst;
+            }
+            std::vector<uint32_t> chunks;
+            uint64_t wsegs = 0;
+            const size_t nchunks = window_batch_plan(g, ixt, rects.data(), dsts.data(), n, p->h_wdesc.p, chunks, &wsegs);
+            if (nchunks) memcpy((uint8_t *)p->h_wdesc.p + dbytes, chunks.data(), 4 * nchunks);
+            uint32_t *d_status = (uint32_t *)p->d_wst.p;
+            HIPOK(hipMemcpyAsync(p->d_wdesc.p, p->h_wdesc.p, dbytes + 4 * nchunks, hipMemcpyHostToDevice, st));
+            if (hipMemsetAsync(d_status, 0, stbytes, st) != hipSuccess) return fail();
+            if (launch_decode_windows(g, plan, in32, in_bit0, (uint64_t)p->s_size * 8, p->h_wdesc.p, p->d_wdesc.p, n,
+                                      (const uint32_t *)((const uint8_t *)p->d_wdesc.p + dbytes), nchunks, d_status, st, ixt)) return fail();
+            hipError_t e = hipMemcpyAsync(p->h_wst.p, d_status, stbytes, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = wait_stream(st);
+            if (e != hipSuccess) { set_error("window batch kernel", (int)e); return fail(); }
+            const uint32_t *status = (const uint32_t *)p->h_wst.p;
+            segs = (size_t)wsegs;
+            // word 0: a table chunk failed its check, or the table's end lies beyond the stream's -- no window keeps its shortcut
+            for (size_t i = 0; i < n && !status[0]; i++)
+                if (!status[1 + i]) {
+                    if (!dequantize(i)) return fail();
+                    p->wins_path[i] = 1; todo--;
+                }
+        } else if (decode_strips_ok(g, plan, ixt)) {
+            // the windows' block rows as ranges of segments, merged: a segment is decoded once, whoever asks for it
+            if (!p->d_win.ensure(total) || !p->d_ws.ensure(plan.ws_bytes)) { p->error = QB3E_LIBERR; return 0; }
+            std::vector<std::pair<uint64_t, uint64_t>> rg(n);
+            for (size_t i = 0; i < n; i++) {
+                const uint64_t by0 = std::min<uint64_t>(wins[i].y0 / 4, g.nby - 1), by1 = std::min<uint64_t>((wins[i].y0 + wins[i].h - 1) / 4, g.nby - 1);
+                rg[i] = { by0 * g.nbx / g.seg_blocks, ((by1 + 1) * g.nbx - 1) / g.seg_blocks + 1 };
+            }
+            std::sort(rg.begin(), rg.end());
+            size_t m = 0;
+            for (size_t i = 1; i < n; i++) {
+                if (rg[i].first <= rg[m].second) rg[m].second = std::max(rg[m].second, rg[i].second);
+                else rg[++m] = rg[i];
+            }
+            uint32_t *d_status = nullptr, status = 1;
+            for (size_t k = 0; k <= m; k++) {               // the first with first-strip semantics: status zeroed, table checked
+                const DecStrip strip = { rg[k].first, rg[k].second - rg[k].first, k == 0 };
+                if (launch_decode(g, plan, in32, in_bit0, (uint64_t)p->s_size * 8, p->d_win.p, nullptr, p->d_ws.p, &d_status, st, TileBatch(), nullptr, ixt,
+                                  nullptr, 0, false, 16, &strip)) return fail();
+                segs += (size_t)(rg[k].second - rg[k].first);
+            }
+            if (launch_window_tail_check(g, (uint64_t)p->s_size * 8, d_status, st, ixt)) return fail();
+            const hipError_t e = fetch_small(&status, d_status, 4, st);
+            if (e != hipSuccess) { set_error("window strips", (int)e); return fail(); }
+            if (!status) {
+                for (size_t i = 0; i < n; i++)
+                    if (!window_crop(p, p->d_win.p, call_of(i), wins[i].dst, hipMemcpyDeviceToDevice, st, false) || !dequantize(i)) return fail();
+                if (hipStreamSynchronize(st) != hipSuccess) return fail();      // (the scratch raster is the handle's: the next call may come on another stream)
+                for (size_t i = 0; i < n; i++) p->wins_path[i] = 2;
+                todo = 0;
+            }
+        }
+        prof_collect();
+        if (!todo) p->last_status = 0;
+    }
+    if (todo) {
+        // a raster no shortcut takes, a table that failed its check, segments that did not decode, a stream that ends early: ONE
+        // whole decode for all the windows that are left; what a shortcut wrote to them is overwritten by the crop
+        if (!p->d_win.ensure(total)) { p->error = QB3E_LIBERR; return 0; }
+        const size_t keep = p->stride;
+        p->stride = 0;                                      // (the scratch raster is tight; the caller's setting is for qb3_read_data)
+        const size_t got = decode_common(p, nullptr, d_src, p->d_win.p, d_index, st);
+        p->stride = keep;
+        if (got) {
+            for (size_t i = 0; i < n; i++)
+                if (!p->wins_path[i] && !window_crop(p, p->d_win.p, call_of(i), wins[i].dst, hipMemcpyDeviceToDevice, st, false)) return fail();
+            if (hipStreamSynchronize(st) != hipSuccess) return fail();
+            for (size_t i = 0; i < n; i++) if (!p->wins_path[i]) p->wins_path[i] = 3;
+            if (coded) segs += (size_t)g.nseg;
+        }
+    }
+    size_t done = 0;
+    for (size_t i = 0; i < n; i++) done += p->wins_path[i] != 0;
+    p->win_path = p->wins_path[n - 1]; p->win_segs = segs;
+    return done;
+}
+
+QB3_API size_t qb3x_decode_windows_device(decsp p, const void *d_src, const void *d_index, const qb3x_window *wins, size_t n, void *stream) {
+    if (!p || !d_src || ((uintptr_t)d_src & 3)) { if (p) p->error = QB3E_EINV; return 0; }
+    return abi_guard<size_t>(0, [&]() -> size_t {
+        if (!windows_check(p, wins, n)) return 0;
+        return windows_device(p, d_src, d_index, wins, n, (hipStream_t)stream);
+    });
+}
+
+QB3_API size_t qb3x_read_windows(decsp p, const qb3x_window *wins, size_t n) {
+    if (!p) return 0;
+    return abi_guard<size_t>(0, [&]() -> size_t {
+        if (!windows_check(p, wins, n)) return 0;
+        const size_t tsz = szof(p->type), pix = p->nbands * tsz, line = p->xsize * pix;
+        const size_t data_off = (size_t)(p->s_in - p->s_start), csize = data_off + p->s_size;
+        if (p->hdr_avail < csize) { p->error = QB3E_EINV; return 0; }        // (a handle over a copy of the container's head only: as qb3_read_data)
+        p->win_path = 0; p->win_segs = 0;
+        p->wins_path.assign(n, 0);
+        if (p->mode == QB3M_STORED) {           // raw pixels: cropped on the host, no device needed
+            if (p->s_size != qb3_decoded_size(p)) { p->error = QB3E_EINV; return 0; }
+            for (size_t i = 0; i < n; i++) {
+                const qb3x_window &w = wins[i];
+                const size_t stride = w.dst_stride ? w.dst_stride : w.w * p->nbands;
+                for (size_t y = 0; y < w.h; y++) memcpy((uint8_t *)w.dst + y * stride * tsz, p->s_in + (w.y0 + y) * line + w.x0 * pix, w.w * pix);
+                p->wins_path[i] = 3;
+            }
+            p->win_path = 3;
+            return n;
+        }
+        if (p->xsize * p->ysize < 16) { p->error = QB3E_EINV; return 0; }
+        if (!device_ok()) { p->error = QB3E_LIBERR; return 0; }
+        // the whole container goes up ONCE; the windows are decoded back to back into one device buffer (each starts on a dword)
+        // and come down one by one, each with its stride
+        hipStream_t st = nullptr;
+        std::vector<qb3x_window> dw(wins, wins + n);
+        size_t wbytes = 0;
+        for (size_t i = 0; i < n; i++) wbytes += (wins[i].h * wins[i].w * pix + 3) & ~(size_t)3;
+        if (!p->d_wsrc.ensure(csize + 8) || !p->d_wout.ensure(wbytes)) { p->error = QB3E_LIBERR; return 0; }
+        wbytes = 0;
+        for (size_t i = 0; i < n; i++) {
+            dw[i].dst = (uint8_t *)p->d_wout.p + wbytes; dw[i].dst_stride = 0;
+            wbytes += (wins[i].h * wins[i].w * pix + 3) & ~(size_t)3;
+        }
+        if (!upload(p->stager, p->d_wsrc.p, p->s_start, csize, st)) { p->error = QB3E_LIBERR; return 0; }
+        HIPOK(hipMemsetAsync((uint8_t *)p->d_wsrc.p + csize, 0, 8, st));      // (a stream that ends early reads as zeros behind its end)
+        if (!windows_device(p, p->d_wsrc.p, nullptr, dw.data(), n, st)) return 0;
+        size_t done = 0;
+        for (size_t i = 0; i < n; i++) {
+            if (!p->wins_path[i]) continue;
+            const qb3x_window &w = wins[i];
+            const size_t stride = w.dst_stride ? w.dst_stride : w.w * p->nbands, wline = w.w * pix;
+            HIPOK(hipMemcpy2DAsync(w.dst, stride * tsz, dw[i].dst, wline, wline, w.h, hipMemcpyDeviceToHost, st));
+            done++;
+        }
+        HIPOK(hipStreamSynchronize(st));
+        return done;
+    });
+}
+
+QB3_API int qb3x_window_ok(const decsp p, size_t i) { return (p && i < p->wins_path.size() && p->wins_path[i]) ? 1 : 0; }
+QB3_API int qb3x_window_path(const decsp p, size_t i) { return (p && i < p->wins_path.size()) ? p->wins_path[i] : 0; }
 
 QB3_API size_t qb3x_window_segments(const decsp p, size_t x0, size_t y0, size_t w, size_t h, size_t *blocks_per_segment) {
     if (blocks_per_segment) *blocks_per_segment = 0;

@@ -3,6 +3,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <vector>
 
 namespace qb3dev {
 
@@ -255,6 +256,21 @@ int launch_decode_window(const Geometry &g, const DecPlan &plan, const uint32_t 
 // behind a strip of launch_decode (which has checked the table): status bit 2 when the table's last entry lies beyond the stream's end
 // -- a stream cut short, which only the whole decode may judge
 int launch_window_tail_check(const Geometry &g, uint64_t in_bits, uint32_t *status, void *stream, const IxTable &ix);
+
+// A batch of windows of one raster (k_dec_wins.hip): one launch decodes all of them, a status word per window.
+// window_batch_plan fills n descriptors of WIN_DESC_BYTES each at `descs` (host memory the caller then copies to the device as it
+// is), the sorted list of table chunks the launch has to check, and the sum of the windows' segment counts; it returns the list's
+// length.  launch_decode_windows takes the descriptors' host and device copies, the chunk list on the device and n + 1 zeroed status
+// words (word 0: the table's checks, call wide; word 1 + i: window i).  Does not synchronise.  Returns hipError_t as int.
+constexpr size_t WIN_DESC_BYTES = 64;
+// waves of one launch: 2^22 workgroups of four, well inside what a grid may hold (2^32 threads).  A batch beyond it is split in front
+// of the window that would exceed it; one window alone stays below it (at most 2^14 block rows of 257 segments)
+constexpr uint64_t WIN_LAUNCH_WAVES = 1ull << 24;
+size_t window_batch_plan(const Geometry &g, const IxTable &ix, const WinRect *rects, void *const *dsts, size_t n, void *descs,
+                         std::vector<uint32_t> &chunks, uint64_t *segments);
+int launch_decode_windows(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
+                          const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
+                          uint32_t *d_status, void *stream, const IxTable &ix);
 
 // The RLE0 byte pass of the *_RLE modes on device buffers (k_rle0.hip; reference QB3encode.cpp:271-332, QB3decode.cpp:267-307).
 // ws: rle0_ws_bytes(n) bytes of device memory.  rle0_device_size returns the size of the coded (decode = false) or

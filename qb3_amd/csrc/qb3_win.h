@@ -1,0 +1,221 @@
+// qb3_amd/csrc/qb3_win.h -- what the window kernels share (k_dec_win.hip: one window a launch; k_dec_wins.hip: a batch of windows a
+// launch): the per-window numbers, the check of the table's end, and the wave's work -- a segment decoded from its table entry, its
+// blocks clipped to the window and stored.  The comment at the head of k_dec_win.hip describes mapping, clipping and trust.
+#pragma once
+#include "qb3_px.h"
+
+namespace qb3dev {
+
+// A window on the device: 64 bytes.  The single call passes it as a kernel argument, a batch as an array in device memory
+struct WinDesc {
+    uint8_t *dst;                   // the window's first byte
+    uint64_t dstride;               // bytes between the window's rows
+    uint32_t wx0, wy0, wx1, wy1;    // the window in raster pixels: [wx0, wx1) x [wy0, wy1)
+    uint32_t bx0, bx1, by0, by1;    // ... in blocks, both ends included
+    uint32_t per_row, nwaves;       // waves per block row of the window; rows * per_row
+    uint32_t wave0;                 // a batch: waves of the launch in front of this window's (the exclusive prefix of nwaves)
+    uint32_t pad_;
+};
+static_assert(sizeof(WinDesc) == 64, "WinDesc is read with scalar loads of sixteen dwords");
+
+// the window's blocks by the geometry rule (pixel x is held by block min(x / 4, nbx - 1)) and the waves that decode them; the
+// caller has checked that the window is not empty and lies inside the raster
+inline void window_desc(const Geometry &g, const WinRect &r, void *dst, WinDesc *w) {
+    w->dst = (uint8_t *)dst; w->dstride = r.stride * g.tsz;
+    w->wx0 = r.x0; w->wy0 = r.y0; w->wx1 = r.x0 + r.w; w->wy1 = r.y0 + r.h;
+    w->bx0 = std::min(r.x0 / 4, g.nbx - 1); w->bx1 = std::min((r.x0 + r.w - 1) / 4, g.nbx - 1);
+    w->by0 = std::min(r.y0 / 4, g.nby - 1); w->by1 = std::min((r.y0 + r.h - 1) / 4, g.nby - 1);
+    // the most segments the run of bx1 - bx0 + 1 blocks of a row touches: it starts anywhere in a segment, unless rows start where segments do
+    const uint32_t n = w->bx1 - w->bx0 + 1;
+    w->per_row = (g.nbx % 64 == 0) ? (w->bx0 % 64 + n - 1) / 64 + 1 : (n + 62) / 64 + 1;
+    w->nwaves = (w->by1 - w->by0 + 1) * w->per_row;
+    w->wave0 = 0; w->pad_ = 0;
+}
+// what a window kernel takes from the raster, the stream and the table (status: the word ix_check_chunk and ix_tail_check raise bits in)
+void window_dec_args(DecArgs &a, const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
+                     uint32_t *status, const IxTable &ix);
+
+// position of the table's last entry against the stream's length: a stream that ends before its last segment starts was cut short
+__device__ __forceinline__ void ix_tail_check(const DecArgs &a) {
+    const uint8_t *e = ix_entry_at(a.ix, a.ix_per_chunk, a.ix_E, a.ix_pad, a.ix_K - 1);
+    uint64_t v = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 6; i++) v |= (uint64_t)e[i] << (8 * i);
+    if (v > a.in_bits) atomicOr(a.status, 4u);
+}
+
+// Wave `wid` of window w (wave: its number in the workgroup of four; both wave uniform): the k-th segment of one of the window's block
+// rows, decoded as dec_px_kernel's BL branch does, stored where the window's blocks go.  status: the word this window's failures go to.
+// Every wave of the workgroup comes here (there is one workgroup barrier); smem: the launch's dynamic LDS, at LDS address 0.
+template <int B, bool RGB, uint64_t ORDER, bool STEP>
+__device__ __forceinline__ void win_decode_wave(const DecArgs &a, const WinDesc &w, uint32_t *status, uint8_t *smem, uint32_t wave, uint32_t wid) {
+    constexpr int NW = (B + 1) / 2;                     // 32-bit words of a scan packed 16 bits per band
+    constexpr uint32_t NB = 64;                         // blocks of a segment
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t nbx = a.g.nbx;
+
+    uint32_t *tab = (uint32_t *)smem;                   // 4 KB, at LDS address 0 (the table addressing relies on it)
+    uint32_t *stage = tab + 1024 + wave * (a.in_cap_dw + 8);
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t *)smem;
+    const uint32_t stage_bit0 = 8 * (lds0 + (uint32_t)((uint8_t *)stage - smem));
+    // the wave's segment: k-th of block row by0 + r, unless the row has no such segment or a row above has it already
+    const uint32_t r = wid / w.per_row, k = wid - r * w.per_row;
+    const uint32_t row0 = (w.by0 + r) * nbx;           // (nblocks <= 2^28)
+    const uint32_t seg = (row0 + w.bx0) / NB + k;
+    bool live = wid < w.nwaves && seg <= (row0 + w.bx1) / NB;
+    if (r > 0 && seg <= (row0 - nbx + w.bx1) / NB) live = false;
+    const uint32_t segc = live ? seg : 0;
+    const uint32_t g0 = segc * NB, nblocks = (uint32_t)a.g.nblocks;
+    const uint32_t nb_here = (nblocks - g0 < NB) ? nblocks - g0 : NB;
+    const bool act = live && lane < nb_here;
+    uint64_t P0, P1;
+    uint32_t rg0[B], pv0[B], blen = 0;
+    {
+        const uint8_t *e = ix_entry_at(a.ix, a.ix_per_chunk, a.ix_E, a.ix_pad, segc);
+        auto pos6 = [](const uint8_t *q) { uint64_t v = 0;
+#pragma unroll
+            for (uint32_t i = 0; i < 6; i++) v |= (uint64_t)q[i] << (8 * i);
+            return v; };
+        P0 = pos6(e);
+        P1 = ((uint64_t)segc + 1 < a.g.nseg) ? pos6(ix_entry_at(a.ix, a.ix_per_chunk, a.ix_E, a.ix_pad, segc + 1)) : a.in_bits;
+#pragma unroll
+        for (int c = 0; c < B; c++) { rg0[c] = e[6 + c] & 7u; pv0[c] = e[6 + B + c]; }
+        const uint8_t *bl = e + 6 + 2 * B + ((IX_BL_BITS * lane) >> 3);
+        blen = act ? (((uint32_t)bl[0] | (uint32_t)bl[1] << 8) >> ((IX_BL_BITS * lane) & 7)) & ((1u << IX_BL_BITS) - 1) : 0u;
+    }
+    for (uint32_t i = tid; i < 256; i += blockDim.x) ((uint4 *)tab)[i] = ((const uint4 *)px_dec_tab.e)[i];
+    __syncthreads();                                    // the only workgroup barrier
+    if (!live) return;
+    const uint64_t w0 = (a.in_bit0 + P0) >> 5;
+    const uint64_t endw_abs = (a.in_bit0 + a.in_bits + 31) >> 5;
+    const uint64_t ndw64 = ((a.in_bit0 + P1 + 31) >> 5) - w0;
+    // the staging area holds the longest valid segment; a table that says otherwise is not this stream's
+    const bool fits = ndw64 <= a.in_cap_dw && lds0 == 0;
+    const uint32_t ndw = fits ? (uint32_t)ndw64 : 0;
+    for (uint32_t base = 0; base < ndw + 8; base += 512) {          // eight loads in flight per lane, then eight LDS stores
+        uint32_t sw[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint32_t i = base + lane + 64 * j;
+            sw[j] = (i < ndw && w0 + i < endw_abs) ? a.in32[w0 + i] : 0u;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint32_t i = base + lane + 64 * j;
+            if (i < ndw + 8) stage[i] = sw[j];
+        }
+    }
+    // the wave reads what its own lanes staged: LDS operations of a wave execute in order, the fence is for the compiler
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+    const uint32_t limit = stage_bit0 + 32 * ndw;       // no unit starts beyond the staged bits (8 zero words follow)
+    const uint32_t cpos = stage_bit0 + (uint32_t)(a.in_bit0 + P0 - 32 * w0);
+    bool bad = !fits;
+    const uint32_t binc = wave_iscan32(blen);           // inclusive: lane 63 holds the bits of the segment
+    uint32_t pos = cpos + binc - blen;
+    uint32_t rp[B][8], spk[NW], sinc[NW];
+#pragma unroll
+    for (int j = 0; j < NW; j++) spk[j] = 0;
+    // band after band: the switch, the band's rungs across the segment (a scan of the switches), the unit, and where it
+    // ended is where the next band's unit starts
+    const uint32_t blk_end = pos + blen;
+#pragma unroll
+    for (int c = 0; c < B; c++) {
+        pos = pos < limit ? pos : limit;
+        bool sig; uint32_t csl;
+        const uint32_t d = px_switch(pos, &csl, &sig);
+        if (act && sig && STEP) bad = true;             // common-factor / index unit: not handled here
+        const uint32_t rung = (rg0[c] + wave_iscan32(act ? d : 0u)) & 7u;
+        uint32_t end;
+        const uint32_t tot = px_group<STEP>(pos + csl, rung, rp[c], &end) & 0xffu;
+        spk[c >> 1] |= (act ? tot : 0u) << (16 * (c & 1));
+        pos = end;
+    }
+    if (act && pos != blk_end) bad = true;              // the table's lengths are not this stream's
+#pragma unroll
+    for (int j = 0; j < NW; j++) sinc[j] = wave_iscan32(spk[j]);
+
+    const uint32_t g = g0 + lane, by = g / nbx, bx = g - by * nbx;
+    if (act && bx >= w.bx0 && bx <= w.bx1 && by >= w.by0 && by <= w.by1) {
+        // entering value, then the core band (reference QB3decode.h:560-567)
+#pragma unroll
+        for (int c = 0; c < B; c++) {
+            const uint32_t pv = pv0[c] + (((sinc[c >> 1] - spk[c >> 1]) >> (16 * (c & 1))) & 0xffffu);
+#pragma unroll
+            for (int j = 0; j < 8; j++) rp[c][j] = pk_add16(rp[c][j], (pv & 0xffu) * 0x00010001u);
+        }
+#pragma unroll
+        for (int c = 0; c < B; c++) {
+            const int cb = core_of<B, RGB>(c);
+            if (cb != c)
+#pragma unroll
+                for (int j = 0; j < 8; j++) rp[c][j] = pk_add16(rp[c][j], rp[cb][j]);
+        }
+        // the block's real pixel origin (last column / row shifted, not padded), clipped to the window
+        const uint32_t xb = (4 * bx + 4 > a.g.w) ? a.g.w - 4 : 4 * bx;
+        const uint32_t yb = (4 * by + 4 > a.g.h) ? a.g.h - 4 : 4 * by;
+        // (a shifted last block repeats pixels of its neighbour, which holds them by the rule: it stores its own columns / rows only,
+        // so that a stream whose two copies differ -- a damaged one -- still gives every pixel one value)
+        const bool whole = xb == 4 * bx && xb >= w.wx0 && xb + 4 <= w.wx1;     // all four columns are the block's and the window's
+        uint32_t colmask = 0;                                       // bit x: column xb + x is the block's and the window's
+#pragma unroll
+        for (uint32_t x = 0; x < 4; x++) colmask |= (xb + x >= 4 * bx && xb + x >= w.wx0 && xb + x < w.wx1) ? 1u << x : 0u;
+        // byte offset of the block's first row in the window (an edge block starts left of or above it: only the bytes under
+        // the masks are addressed)
+        const int64_t off0 = ((int64_t)yb - (int64_t)w.wy0) * (int64_t)w.dstride + ((int64_t)xb - (int64_t)w.wx0) * B;
+#pragma unroll
+        for (int y = 0; y < 4; y++) {
+            uint32_t ow[B];
+#pragma unroll
+            for (int j = 0; j < B; j++) {
+                // byte i of output dword j is band (4j+i)%B of pixel x = (4j+i)/B: low byte of a 16-bit lane
+                uint32_t half2[2];
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const int b0 = 4 * j + 2 * h, b1 = b0 + 1;
+                    const int i0 = curve_pos_of(ORDER, b0 / B, y), i1 = curve_pos_of(ORDER, b1 / B, y);
+                    // v_perm_b32: selector bytes 0..3 pick from the second operand, 4..7 from the first
+                    half2[h] = __builtin_amdgcn_perm(rp[b1 % B][i1 >> 1], rp[b0 % B][i0 >> 1],
+                                                     (uint32_t)((4 + 2 * (i1 & 1)) << 8 | (2 * (i0 & 1))));
+                }
+                ow[j] = __builtin_amdgcn_perm(half2[1], half2[0], 0x05040100u);
+            }
+            if (yb + y < 4 * by || yb + y < w.wy0 || yb + y >= w.wy1) continue;     // the neighbour's row, or one above or below the window
+            uint8_t *row = w.dst + (off0 + (int64_t)y * (int64_t)w.dstride);
+            if (!whole) {           // edge block: the bytes of the window's columns, one by one
+#pragma unroll
+                for (int i = 0; i < 4 * B; i++)
+                    if ((colmask >> (i / B)) & 1u) row[i] = (uint8_t)(ow[i >> 2] >> (8 * (i & 3)));
+                continue;
+            }
+            const uint32_t al = (uint32_t)(uintptr_t)row & 3;
+            if (al == 0) {
+#pragma unroll
+                for (int j = 0; j < B; j++) ((uint32_t *)row)[j] = ow[j];
+            } else {        // unaligned row: head bytes, the aligned dwords inside it, tail bytes -- only the row's own 4*B bytes
+                const uint32_t head = 4 - al, sh = 8 * head;            // bytes before the first aligned dword
+#pragma unroll
+                for (uint32_t t = 0; t < 3; t++) if (t < head) row[t] = (uint8_t)(ow[0] >> (8 * t));
+                uint32_t *mid = (uint32_t *)(row + head);
+#pragma unroll
+                for (int j = 0; j + 1 < B; j++) mid[j] = __builtin_amdgcn_alignbit(ow[j + 1], ow[j], sh);
+                uint8_t *tail = row + head + 4 * (B - 1);               // the last `al` bytes
+                const uint32_t last = ow[B - 1] >> sh;
+#pragma unroll
+                for (uint32_t t = 0; t < 3; t++) if (t < al) tail[t] = (uint8_t)(last >> (8 * t));
+            }
+        }
+    }
+    if (bad) atomicOr(status, fits ? 1u : 8u);
+    // a segment that reaches beyond the stream's end (a stream cut short): the whole-raster decode decides what its pixels are
+    if (lane == 0 && (P1 > a.in_bits || P1 < P0)) atomicOr(status, 4u);
+    if (lane == 63 && (uint64_t)seg == a.g.nseg - 1 && fits) {      // reference: more than 7 unused bits at the end is a failure
+        const uint64_t used = (uint64_t)(cpos + binc - stage_bit0) + 32 * w0 - a.in_bit0;
+        if (used > a.in_bits) atomicOr(status, 4u);
+        else if (a.in_bits - used > 7) atomicOr(status, 2u);
+    }
+}
+
+}  // namespace qb3dev

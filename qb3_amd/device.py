@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import lib, last_error, TYPESIZE, NP_DTYPE, QB3M_FTL, _sz
+from . import lib, last_error, TYPESIZE, NP_DTYPE, QB3M_FTL, _sz, window_array
 
 _vp = C.c_void_p
 
@@ -122,6 +122,36 @@ class DeviceDecoder:
         if n == 0:
             raise RuntimeError(f"qb3x_decode_window_device failed: {last_error()}")
         return out.view(-1)[:nbytes].view(getattr(torch, NP_DTYPE[dt])).view(h, w, self.bands)
+
+    def decode_windows(self, d_stream, rects, out=None, index=None):
+        """the windows (x0, y0, w, h) of `rects` in ONE call (qb3x_decode_windows_device): a list of device tensors of shape
+        (h, w, bands) and the raster's type.  out: a list of contiguous uint8 device tensors, one a window, of at least the
+        window's bytes each, to decode into (they may be views of one buffer; they must not overlap)."""
+        assert d_stream.is_cuda
+        dt = lib.qb3_get_type(self.p)
+        rects = [tuple(int(v) for v in r) for r in rects]
+        sizes = [h * w * self.bands * TYPESIZE[dt] for _, _, w, h in rects]
+        if out is None:                 # one allocation, every window on a dword
+            offs = [0]
+            for nb in sizes:
+                offs.append(offs[-1] + (nb + 3) // 4 * 4)
+            buf = torch.empty(max(offs[-1], 4), dtype=torch.uint8, device=d_stream.device)
+            out = [buf[offs[i]:offs[i] + sizes[i]] for i in range(len(rects))]
+        assert len(out) == len(rects)
+        for o, nb in zip(out, sizes):
+            assert o.is_cuda and o.is_contiguous() and o.dtype == torch.uint8 and o.numel() >= nb
+        wins = window_array(rects, [o.data_ptr() for o in out])
+        n = lib.qb3x_decode_windows_device(self.p, _vp(d_stream.data_ptr()), _vp(index.data_ptr()) if index is not None else None,
+                                           wins, len(rects), _stream_ptr())
+        self._nwin = len(rects)
+        if n != len(rects):
+            raise RuntimeError(f"qb3x_decode_windows_device wrote {n} of {len(rects)} windows: {last_error()}")
+        return [o.view(-1)[:nb].view(getattr(torch, NP_DTYPE[dt])).view(h, w, self.bands) for o, nb, (_, _, w, h) in zip(out, sizes, rects)]
+
+    @property
+    def last_windows(self):
+        """the paths of the last decode_windows, one a window (0: not written; 1, 2, 3 as last_window)"""
+        return [lib.qb3x_window_path(self.p, i) for i in range(getattr(self, "_nwin", 0))]
 
     @property
     def last_window(self):

@@ -4,7 +4,13 @@ the whole qb3x_decode_device into a buffer of its own, then a strided device cop
 block rows + crop, path 2); windows of 256^2, 1024^2, 4096^2 and the whole raster at an origin that is not a multiple of 256.
 Events on the caller's stream around N calls, both ways alternating in the same run; the window kernel's own time from the
 library's profile (dec_window) in a pass of its own.  One JSON line per window.
-Without CASE every raster runs in a child process of its own under a time limit, and the first failure ends the run."""
+Without CASE every raster runs in a child process of its own under a time limit, and the first failure ends the run.
+
+tools/window_bench.py --batch [CASE] -- the batch call (qb3x_decode_windows_device) against the same windows through single calls on
+the same handle: 64 windows of 256^2 and 64 of 1024^2 of the headline raster at seeded random origins that are not multiples of 256
+(path 1: one launch against 64), and 16 windows of 256^2 of a plain 4096 x 4096 x 3 container (path 3: one whole decode against
+16).  Same timing: events on the caller's stream, alternating over three rounds in one process, dec_window's time in a pass of its
+own.  One JSON line per case."""
 import json
 import os
 import subprocess
@@ -74,9 +80,75 @@ def run(case):
                           "decode_and_crop_ms": [round(t, 4) for t in t_old], "kernel_ms": kern}), flush=True)
 
 
+BATCH_CASES = {"batch256": (16384, 16384, 3, 2, 64, 256), "batch1024": (16384, 16384, 3, 2, 64, 1024), "batch_path3": (4096, 4096, 3, 0, 16, 256)}
+
+
+def run_batch(case):
+    import numpy as np
+    import torch
+    from qb3_amd import synth, device as qdev
+    w, h, b, level, count, side = BATCH_CASES[case]
+    img = synth.generate(w, h, b, 0, "NOISY3", 3)
+    raw = img.reshape(-1).view(torch.uint8)
+    enc = qdev.DeviceEncoder(w, h, b, 0, mode=8, want_index=False, index_chunk=level)
+    dst, n, _ = enc.encode(raw)
+    dec = qdev.DeviceDecoder(dst, n)
+    rng = np.random.default_rng(64 + side)
+    rects = []
+    while len(rects) < count:
+        x0, y0 = int(rng.integers(0, w - side + 1)), int(rng.integers(0, h - side + 1))
+        if x0 % 256 and y0 % 256:
+            rects.append((x0, y0, side, side))
+    nb = side * side * b
+    buf = torch.empty(count * nb, dtype=torch.uint8, device="cuda")
+    outs = [buf[i * nb:(i + 1) * nb] for i in range(count)]
+
+    def batch():
+        dec.decode_windows(dst, rects, out=outs)
+
+    def singles():
+        for (x0, y0, ww, hh), o in zip(rects, outs):
+            dec.decode_window(dst, x0, y0, ww, hh, out=o)
+
+    rows = raw.view(h, -1)
+    for fn in (singles, batch):                         # both ways give the crop
+        buf.zero_()
+        fn()
+        for (x0, y0, ww, hh), o in zip(rects, outs):
+            assert torch.equal(o.view(hh, ww * b), rows[y0:y0 + hh, x0 * b:(x0 + ww) * b]), "window bytes"
+    paths = dec.last_windows
+    segs = dec.last_window[1]
+    reps = 50 if level else 10
+    t_batch, t_single = [], []
+    for _ in range(3):                                  # alternating, three rounds each
+        t_batch.append(timed(batch, reps))
+        t_single.append(timed(singles, reps))
+    qdev.profile_reset()
+    qdev.profile_enable(1)
+    for _ in range(20):
+        batch()
+    torch.cuda.synchronize()
+    qdev.profile_enable(0)
+    prof = qdev.profile_report()
+    kern = {k: round(v[0] / v[1], 4) for k, v in prof.items() if k in ("dec_window", "dec_units")}
+    launches = {k: v[1] / 20 for k, v in prof.items() if k == "dec_window"}
+    print(json.dumps({"case": case, "windows": count, "side": side, "paths": sorted(set(paths)), "segments": segs,
+                      "batch_ms": [round(t, 4) for t in t_batch], "single_calls_ms": [round(t, 4) for t in t_single],
+                      "ratio": round(min(t_batch) / min(t_single), 4), "kernel_ms": kern, "launches_per_call": launches}), flush=True)
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1:
-        run(sys.argv[1])
+    args = sys.argv[1:]
+    if args and args[0] == "--batch":
+        if len(args) > 1:
+            run_batch(args[1])
+        else:
+            for case in BATCH_CASES:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--batch", case], timeout=300)
+                if r.returncode:
+                    sys.exit("window_bench: %s ended with status %d; nothing more is run" % (case, r.returncode))
+    elif args:
+        run(args[0])
     else:
         for case in CASES:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), case], timeout=420)
