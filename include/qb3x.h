@@ -219,6 +219,39 @@ size_t qb3x_decoder_table_entries(const decsp p);
  * in QB3M_CF_H from the container alone: 1.0 ms; 2.3 before). */
 void qb3x_set_encoder_index_chunk(encsp p, int on);
 
+/* Reindex: a restart table for a container that exists -- a file the reference or GDAL wrote, one of this library's with a table of
+ * another version or segment size -- without decoding to pixels and encoding again: no stream bit changes, nothing has to be restated
+ * (mode, band map, quanta and scan order stay in the header as they are), and the plain walk is paid once.  No counterpart in the
+ * reference, whose stream has no restart points (QB3decode.h:445-454).
+ * level 0: no table (the reference's bytes), 1: positions and states, 2: with block / unit lengths where the raster has them
+ * (qb3x_set_encoder_index_chunk's values).
+ * The output is the source with every "ix" / "zz" chunk removed and, for levels 1 and 2, directly in front of "DT" the table chunks
+ * this library's ENCODER writes for the raster at that level: the same segment size, entry layout (version 3, checks sealed) and pads.
+ * Every other header byte (CB, QV, SC, the mode, foreign ignorable chunks) stays, in order; every byte behind "DT" is unchanged.  So for
+ * the containers C0, C1, C2 the encoder writes for one raster with qb3x_set_encoder_index_chunk 0, 1, 2: reindex(Ca, level b) == Cb, byte
+ * for byte.  Where the encoder writes no table -- STORED containers, narrow images (a side below 4) -- the output is the source without
+ * its "ix" / "zz" chunks at every level.  A table the source carries is dropped and never trusted, whatever its version, segment size
+ * or state.  A container whose RLE0 pass won keeps its coded bytes and gets the table of the expanded block stream, as from the encoder.
+ * How: the whole decode of the stream WITHOUT a table into a scratch raster the handle owns (qb3_decoded_size bytes of device memory;
+ * the pixels prove the stream sound) leaves a complete index in the handle's workspace; the encoder's own fill code makes the entries
+ * of it (profile name reindex_fill), one more launch writes the kept header, the chunks' heads, pads and checks, "DT", and moves the
+ * coded bytes (reindex_finish).  The call synchronises `stream` once more than the decode does.
+ * qb3x_reindex_size: the size of the new container (what dst_cap must at least be), 0 on error; needs no device.
+ * qb3x_reindex_device: p is a handle past qb3_read_info over a HOST copy of the whole container (the header is rebuilt from it);
+ * d_src the whole container, 4-byte aligned; d_dst 4-byte aligned, not overlapping d_src.  Returns the new container's size, 0 on error.
+ * qb3x_reindex: host buffers; makes and destroys its own handle.  Level 0, STORED and narrow sources need no device; otherwise the
+ * container goes up once and the new one comes down.
+ * Errors (0 returned, no byte written at or behind d_dst + dst_cap):
+ *   QB3E_EINV  a handle that is not past qb3_read_info or holds only a copy of the container's head, a level outside 0..2, dst_cap
+ *              below qb3x_reindex_size, pointers that are NULL or not 4-byte aligned;
+ *   QB3E_ERR   a stream whose walk ends with an error, or with "the stream ended early" (status bit 2, which a decode forgives as the
+ *              reference's reader does): an archive tool must not index a truncated stream -- the table's last entry would lie
+ *              beyond its end.  The destination's contents are then unspecified.  (Bit 6, which lane walked the stream, is no error.)
+ * qb3x_last_decode_status reports the walk's status word as after a decode. */
+size_t qb3x_reindex_size(const decsp p, int level);
+size_t qb3x_reindex_device(decsp p, const void *d_src, void *d_dst, size_t dst_cap, int level, void *stream);
+size_t qb3x_reindex(const void *src, size_t src_size, void *dst, size_t dst_cap, int level);
+
 /* Compatibility switches. */
 #define QB3X_REF_CBAND0 1u      /* decoder: reproduce reference defect (no CB chunk => every band adds band 0,
                                    reference QB3decode.cpp:138 + QB3decode.h:560-567) instead of identity */
@@ -232,7 +265,8 @@ size_t qb3_decode(decsp p, void *destination);                                  
  * events on the launch stream; totals are resolved at the library's own synchronisation points.
  * Kernel names: enc_units, enc_scan, enc_concat, enc_seams, enc_best_units, enc_best_scan, enc_best_recode,
  * dec_index_table, dec_index_serial, dec_index_prev, dec_index_scan, dec_units, dec_segments, dec_window (the window kernel of
- * qb3x_decode_window_device, path 1).
+ * qb3x_decode_window_device, path 1), reindex_fill, reindex_finish (qb3x_reindex_device: the table's entries; everything else of the
+ * new container).
  * level: 0 off, 1 every kernel, 2 all but the microsecond kernels (enc_scan, enc_seams, enc_best_scan), whose two
  * events cost more than they take. */
 void qb3x_profile_enable(int level);

@@ -98,6 +98,9 @@ _PROTOS = {
     "qb3x_header_size_bound": (_sz, [_vp, _sz]),
     "qb3x_decoder_table_entries": (_sz, [_vp]),
     "qb3x_set_decoder_compat": (None, [_vp, C.c_uint]),
+    "qb3x_reindex_size": (_sz, [_vp, C.c_int]),
+    "qb3x_reindex_device": (_sz, [_vp, _vp, _vp, _sz, C.c_int, _vp]),
+    "qb3x_reindex": (_sz, [_vp, _sz, _vp, _sz, C.c_int]),
     "qb3_create_decoder": (_vp, [_vp, _sz, C.POINTER(_sz)]),
     "qb3_decode": (_sz, [_vp, _vp]),
     "qb3x_last_error": (C.c_char_p, []),
@@ -233,3 +236,25 @@ def decode_windows(stream, rects, compat=0):
         return outs
     finally:
         lib.qb3_destroy_decoder(p)
+
+
+def reindex(stream, level):
+    """qb3x_reindex: the container with its restart table dropped (level 0) or replaced by the one this library's encoder writes at
+    level 1 or 2; the coded bytes are not touched.  Returns the new container as a uint8 array."""
+    import numpy as np
+    buf = np.ascontiguousarray(stream, dtype=np.uint8)
+    dims = (_sz * 3)()
+    p = lib.qb3_read_start(_np_ptr(buf), buf.size, dims)
+    if not p:
+        raise ValueError("qb3_read_start rejected the stream")
+    try:
+        cap = lib.qb3x_reindex_size(p, level) if lib.qb3_read_info(p) else 0
+    finally:
+        lib.qb3_destroy_decoder(p)
+    if not cap:
+        raise ValueError("qb3x_reindex_size refused the container or the level")
+    out = np.empty(cap, dtype=np.uint8)
+    n = lib.qb3x_reindex(_np_ptr(buf), buf.size, _np_ptr(out), cap, level)
+    if n == 0:
+        raise RuntimeError(f"qb3x_reindex failed: {last_error()}")
+    return out[:n]

@@ -1,5 +1,6 @@
 // qb3_amd/csrc/k_enc_post.hip -- after the chunks are coded: offsets (scan), concatenation, seams, header, index chunks
 #include "qb3_kernels.h"
+#include "qb3_ix_fill.h"
 
 namespace qb3dev {
 
@@ -279,7 +280,6 @@ __device__ __forceinline__ void finish_seam(const EncArgs &a, uint32_t k, CS cs)
 __global__ void __launch_bounds__(256) enc_finish_kernel(const EncArgs a0) {
     const EncArgs a = enc_for_tile(a0, blockIdx.y);
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x, nthreads = gridDim.x * blockDim.x;
-    const uint32_t B = a.g.bands, tsz = a.g.tsz;
     if ((a.finish_what & 2) && blockIdx.x == 0 && a.hdr_len) {     // the stream starts at out32 + out_bit0 / 8; the prepared header bytes end hdr_back before
         uint8_t *start = (uint8_t *)a.out32 + (a.out_bit0 >> 3) - a.hdr_back;
         for (uint32_t i = threadIdx.x; i < a.hdr_len; i += blockDim.x) start[i] = a0.hdr[i];
@@ -291,31 +291,10 @@ __global__ void __launch_bounds__(256) enc_finish_kernel(const EncArgs a0) {
             a.idx.bitpos[sgi] = bp;
             if (!a.ix_dst || a.ix_coder || sgi % a.ix_spe) continue;       // (a table the coding kernel wrote: enc_concat_kernel's)
             const uint32_t ke = (uint32_t)(sgi / a.ix_spe);        // the segment's entry of the restart table
-            const uint32_t c = ke / a.ix_per_chunk, j = ke - c * a.ix_per_chunk;
-            const uint32_t here = (a.ix_K - c * a.ix_per_chunk < a.ix_per_chunk) ? a.ix_K - c * a.ix_per_chunk : a.ix_per_chunk;   // entries of this chunk
-            uint8_t *chunk = a.ix_dst + (uint64_t)c * (IX_HEAD + IX_PAD + (uint64_t)a.ix_per_chunk * a.ix_E);
-            if (j == 0) {
-                const uint32_t len = IX_HEAD + here * a.ix_E;
-                chunk[0] = 'i'; chunk[1] = 'x'; chunk[2] = (uint8_t)len; chunk[3] = (uint8_t)(len >> 8);
-                chunk[4] = 3; chunk[5] = (a.g.mode == CM_BEST ? 1 : 0) | (a.ix_bl ? 2 : 0); chunk[6] = 0; chunk[7] = 0;      // (bytes 6, 7: ix_seal_kernel)
-                for (uint32_t i = 0; i < 4; i++) chunk[8 + i] = (uint8_t)(a.ix_blocks >> (8 * i));
-                uint8_t *pad = chunk + len;
-                pad[0] = 'z'; pad[1] = 'z'; pad[2] = 4; pad[3] = 0;
-                if (c * a.ix_per_chunk + here == a.ix_K) { pad[4] = 'D'; pad[5] = 'T'; }
-            }
+            const IxFill f = ix_fill_of(a);
+            if (ke % a.ix_per_chunk == 0) ix_write_head(f, ke / a.ix_per_chunk, 0);     // (bytes 6, 7: ix_seal_kernel)
             if (a.ix_bl) continue;              // (entries with block lengths: their fill kernel writes the fixed fields too)
-            uint8_t *e = chunk + IX_HEAD + (uint64_t)j * a.ix_E;
-            for (uint32_t i = 0; i < 6; i++) e[i] = (uint8_t)(bp >> (8 * i));
-            e += 6;
-            for (uint32_t c2 = 0; c2 < B; c2++) e[c2] = a.idx.rung[sgi * B + c2];
-            e += B;
-            const uint8_t *pv = (const uint8_t *)a.idx.prev + sgi * B * tsz;
-            for (uint32_t i = 0; i < B * tsz; i++) e[i] = pv[i];
-            if (a.g.mode == CM_BEST) {
-                e += B * tsz;
-                const uint8_t *cf = (const uint8_t *)a.idx.cf + sgi * B * tsz;
-                for (uint32_t i = 0; i < B * tsz; i++) e[i] = cf[i];
-            }
+            ix_plain_entry(f, sgi, bp);
         }
     if (!(a.finish_what & 1) || k > a.nchunks) return;
     finish_seam(a, k, [&](uint32_t j) { return chunk_start(a, j); });
@@ -353,220 +332,43 @@ __global__ void __launch_bounds__(256) enc_finish_strip_kernel(const EncArgs a0,
     finish_seam(a, k, [&](uint32_t j) { return j >= a.chunk_end ? a.group_sum[strip + 1] : a.group_sum[j / SCAN_GROUP] + a.chunk_off[j]; });
 }
 
-// Block lengths behind the entries' fixed fields (tables of level 2).  A block's bit length is the sum of its units'
-// lengths (the index has them).  Four ten-bit fields are five whole bytes and an entry's 64 blocks are sixteen such
-// groups: a thread per group of four blocks reads their 4 * B length bytes (whole dwords) and writes five bytes of
-// the entry -- no two threads share a byte.
+// The table's entries with fields, one kernel per layout (the bodies: qb3_ix_fill.h, shared with the reindex kernels).
+// 8-bit rasters of 1 / 3 / 4 bands: ten bits per block, a thread per four blocks
 __global__ void __launch_bounds__(256) ix_bl_fill_kernel(const EncArgs a0) {
     const EncArgs a = enc_for_tile(a0, blockIdx.y);
-    static_assert(IX_BL_BITS == 10, "groups of four fields are five bytes");
-    const uint64_t grp = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;       // blocks 4 * grp .. 4 * grp + 3
-    const uint32_t B = a.g.bands;
-    const uint64_t k = grp >> 4;                                                // 16 groups an entry
-    if (k >= a.ix_K) return;
-    const uint64_t nblocks = a.g.nblocks, blk0 = 4 * grp;
-    uint32_t len[4] = {0, 0, 0, 0};
-    if (blk0 + 4 <= nblocks && ((uintptr_t)a.idx.ulen & 3) == 0) {
-        const uint32_t *ul = (const uint32_t *)((const uint8_t *)a.idx.ulen + blk0 * B);    // 4 * B bytes: B dwords
-        if (B == 1) { const uint32_t v = ul[0]; len[0] = v & 255; len[1] = (v >> 8) & 255; len[2] = (v >> 16) & 255; len[3] = v >> 24; }
-        else if (B == 3) {
-            const uint32_t v0 = ul[0], v1 = ul[1], v2 = ul[2];
-            len[0] = (v0 & 255) + ((v0 >> 8) & 255) + ((v0 >> 16) & 255);
-            len[1] = (v0 >> 24) + (v1 & 255) + ((v1 >> 8) & 255);
-            len[2] = ((v1 >> 16) & 255) + (v1 >> 24) + (v2 & 255);
-            len[3] = ((v2 >> 8) & 255) + ((v2 >> 16) & 255) + (v2 >> 24);
-        } else {
-#pragma unroll
-            for (uint32_t q = 0; q < 4; q++) { const uint32_t v = ul[q]; len[q] = (v & 255) + ((v >> 8) & 255) + ((v >> 16) & 255) + (v >> 24); }
-        }
-    } else {
-        const uint8_t *ul = (const uint8_t *)a.idx.ulen + blk0 * B;
-        for (uint32_t q = 0; q < 4; q++)
-            if (blk0 + q < nblocks) for (uint32_t c = 0; c < B; c++) len[q] += ul[q * B + c];
-    }
-    const uint64_t bits = (uint64_t)len[0] | (uint64_t)len[1] << 10 | (uint64_t)len[2] << 20 | (uint64_t)len[3] << 30;
-    const uint32_t c = (uint32_t)(k / a.ix_per_chunk), jj = (uint32_t)(k - (uint64_t)c * a.ix_per_chunk);
-    uint8_t *e0 = a.ix_dst + (uint64_t)c * (IX_HEAD + IX_PAD + (uint64_t)a.ix_per_chunk * a.ix_E) + IX_HEAD + (uint64_t)jj * a.ix_E;
-    uint8_t *e = e0 + 6 + 2 * B + 5 * (uint32_t)(grp & 15);
-#pragma unroll
-    for (uint32_t i = 0; i < 5; i++) e[i] = (uint8_t)(bits >> (8 * i));
-    // the entry's fixed fields (an entry per segment: ix_spe == 1, 8-bit values, no factors): at most 14 bytes, one per thread of
-    // the entry's sixteen
-    const uint32_t t = (uint32_t)(grp & 15);
-    if (t < 6) e0[t] = (uint8_t)(a.idx.bitpos[k] >> (8 * t));
-    else if (t < 6 + B) e0[t] = a.idx.rung[k * B + (t - 6)];
-    else if (t < 6 + 2 * B) e0[t] = ((const uint8_t *)a.idx.prev)[k * B + (t - 6 - B)];
+    ix_bl_fill(ix_fill_of(a), (uint64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
-
-// four 24-bit fields as three dwords at any byte address (global memory takes unaligned dword stores)
-__device__ __forceinline__ void ix_store12(uint8_t *e, const uint32_t (&f)[4]) {
-    typedef uint32_t u32_a1 __attribute__((aligned(1)));
-    u32_a1 *d = (u32_a1 *)e;
-    d[0] = f[0] | f[1] << 24; d[1] = f[1] >> 8 | f[2] << 16; d[2] = f[2] >> 16 | f[3] << 8;
-}
-// The same for common-factor streams with a block table (8-bit grey / RGB / RGBA; 32/64-bit, one band): a three-byte field per
-// block -- its bits (12) and the rungs its units are entered with (8-bit data: 3 bits a band; wide data: the band's whole rung)
-// -- from the index's block table; a thread per four blocks writes twelve bytes and its share of the entry's fixed part
-// (position, rungs, entering values, factors in force: 6 + bands * (1 + 2 * value size) bytes)
+// common-factor streams with a block table: a three-byte field per block, a thread per four blocks
 __global__ void __launch_bounds__(256) ix_bl_best_fill_kernel(const EncArgs a0) {
     const EncArgs a = enc_for_tile(a0, blockIdx.y);
-    const uint64_t grp = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;       // blocks 4 * grp .. 4 * grp + 3
-    const uint32_t B = a.g.bands, tsz = a.g.tsz;
-    const uint64_t k = grp >> 4;                                                // 16 groups an entry (64 blocks)
-    if (k >= a.ix_K) return;
-    const uint64_t nblocks = a.g.nblocks, blk0 = 4 * grp;
-    const uint32_t c = (uint32_t)(k / a.ix_per_chunk), jj = (uint32_t)(k - (uint64_t)c * a.ix_per_chunk);
-    uint8_t *e0 = a.ix_dst + (uint64_t)c * (IX_HEAD + IX_PAD + (uint64_t)a.ix_per_chunk * a.ix_E) + IX_HEAD + (uint64_t)jj * a.ix_E;
-    const uint32_t t = (uint32_t)(grp & 15), fixed = 6 + B * (1 + 2 * tsz);
-    uint8_t *e = e0 + fixed + 4 * IX_BL_BEST_BYTES * t;
-    uint32_t fl[4];
-#pragma unroll
-    for (uint32_t q = 0; q < 4; q++) {
-        const uint32_t bt = blk0 + q < nblocks ? ((const uint32_t *)a.idx.ulen)[blk0 + q] : 0u;
-        uint32_t f = bt & 0xfffu;
-        if (tsz == 1) {
-#pragma unroll
-            for (uint32_t cc = 0; cc < 4; cc++) f |= ((bt >> (16 + 4 * cc)) & 7u) << (12 + 3 * cc);
-        } else f |= ((bt >> 16) & 63u) << 12;
-        fl[q] = f;
-    }
-    ix_store12(e, fl);          // (four three-byte fields: three dwords at whatever address the entry puts them)
-    for (uint32_t i = t; i < fixed; i += 16) {
-        uint8_t v;
-        if (i < 6) v = (uint8_t)(a.idx.bitpos[k] >> (8 * i));
-        else if (i < 6 + B) v = a.idx.rung[k * B + (i - 6)];
-        else if (i < 6 + B + B * tsz) v = ((const uint8_t *)a.idx.prev)[k * B * tsz + (i - 6 - B)];
-        else v = ((const uint8_t *)a.idx.cf)[k * B * tsz + (i - 6 - B - B * tsz)];
-        e0[i] = v;
-    }
+    ix_bl_best_fill(ix_fill_of(a), (uint64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
-
-// The same for 16-bit rasters of four or eight bands: a field is the bit length of a band PAIR (two units), two fields per
-// lane of the decoder's wave (lane = block of the segment x band group of four), 128 fields an entry.  A thread per four
-// fields (two lanes): five whole bytes; the entry's first 6 + 3 * bands threads also write one byte each of its fixed part.
+// 16-bit rasters: ten bits per band pair, a thread per four fields
 __global__ void __launch_bounds__(256) ix_bl16_fill_kernel(const EncArgs a0) {
     const EncArgs a = enc_for_tile(a0, blockIdx.y);
-    static_assert(IX_BL_BITS == 10, "groups of four fields are five bytes");
-    const uint64_t grp = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;       // fields 4 * grp .. 4 * grp + 3 of entry grp / 32
-    // (a single band: one field per lane -- the unit's length -- 64 fields an entry, 16 threads)
-    const uint32_t B = a.g.bands, BG = a.px16_bg, FPL = B == 1 ? 1 : 2, NG = B / BG, NB = 64 / NG, tpe = 16 * FPL;
-    const uint64_t k = grp / tpe;
-    if (k >= a.ix_K) return;
-    const uint32_t t = (uint32_t)(grp - k * tpe);
-    uint64_t bits = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < 4; q++) {
-        const uint32_t field = 4 * t + q, lane = field / FPL, pair = field - lane * FPL;
-        const uint32_t slot = lane / NG, g4 = lane - slot * NG;
-        const uint64_t blk = k * NB + slot;
-        uint32_t len = 0;
-        if (slot < NB && blk < a.g.nblocks) {       // (lanes behind the segment's blocks x groups: nothing)
-            // the lane's bands: BG from band BG * g4; four: the pairs (0,1), (2,3); three: (0,1) and band 2; two: a field a band; one: the unit
-            const uint16_t *ul = (const uint16_t *)a.idx.ulen + blk * B + BG * g4;
-            if (BG == 1) len = ul[0];
-            else if (BG == 2) len = ul[pair];
-            else if (BG == 3) len = pair ? (uint32_t)ul[2] : (uint32_t)ul[0] + ul[1];
-            else len = (uint32_t)ul[2 * pair] + ul[2 * pair + 1];
-        }
-        bits |= (uint64_t)len << (IX_BL_BITS * q);
-    }
-    const uint32_t c = (uint32_t)(k / a.ix_per_chunk), jj = (uint32_t)(k - (uint64_t)c * a.ix_per_chunk);
-    uint8_t *e0 = a.ix_dst + (uint64_t)c * (IX_HEAD + IX_PAD + (uint64_t)a.ix_per_chunk * a.ix_E) + IX_HEAD + (uint64_t)jj * a.ix_E;
-    uint8_t *e = e0 + 6 + 3 * B + 5 * t;
-#pragma unroll
-    for (uint32_t i = 0; i < 5; i++) e[i] = (uint8_t)(bits >> (8 * i));
-    // fixed part: bit position, a rung byte per band, the entering values (two bytes a band): 6 + 3 * B <= 30 bytes
-    if (t < 6) e0[t] = (uint8_t)(a.idx.bitpos[k] >> (8 * t));
-    else if (t < 6 + B) e0[t] = a.idx.rung[k * B + (t - 6)];
-    else if (t < 6 + 3 * B) e0[t] = ((const uint8_t *)a.idx.prev)[k * 2 * B + (t - 6 - B)];
+    ix_bl16_fill(ix_fill_of(a), (uint64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
-
-// 32/64-bit rasters: a twelve-bit length per UNIT of the segment (the unit-parallel decoder wants every unit's place).
-// A thread per two fields: three whole bytes; the entry's threads share its fixed part a byte each.
+// 32/64-bit rasters and the lane-per-unit decoder's: twelve bits per unit, a thread per two fields
 __global__ void __launch_bounds__(256) ix_blw_fill_kernel(const EncArgs a0, const uint32_t tpe) {     // tpe: threads per entry
     const EncArgs a = enc_for_tile(a0, blockIdx.y);
-    static_assert(IX_BL_BITS_WIDE == 12, "pairs of fields are three bytes");
-    const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t B = a.g.bands, tsz = a.g.tsz, upe = a.ix_blocks * B;         // units per entry
-    const uint64_t k = idx / tpe;
-    if (k >= a.ix_K) return;
-    const uint32_t t = (uint32_t)(idx - k * tpe);
-    const uint64_t u0 = k * upe, nunits = a.g.nblocks * B;
-    uint32_t len[2] = {0, 0};
-    for (uint32_t q = 0; q < 2; q++) {
-        const uint32_t f = 2 * t + q;
-        if (f < upe && u0 + f < nunits) len[q] = a.g.ulen_sz == 1 ? (uint32_t)((const uint8_t *)a.idx.ulen)[u0 + f] : (uint32_t)((const uint16_t *)a.idx.ulen)[u0 + f];
-    }
-    const uint32_t bits = len[0] | len[1] << 12;
-    const uint32_t c = (uint32_t)(k / a.ix_per_chunk), jj = (uint32_t)(k - (uint64_t)c * a.ix_per_chunk);
-    uint8_t *e0 = a.ix_dst + (uint64_t)c * (IX_HEAD + IX_PAD + (uint64_t)a.ix_per_chunk * a.ix_E) + IX_HEAD + (uint64_t)jj * a.ix_E;
-    const uint32_t fixed = 6 + B * (1 + tsz), nbytes = (upe * 12 + 7) / 8;
-    uint8_t *e = e0 + fixed + 3 * t;
-    for (uint32_t i = 0; i < 3; i++) if (3 * t + i < nbytes) e[i] = (uint8_t)(bits >> (8 * i));
-    for (uint32_t i = t; i < fixed; i += tpe) {         // bit position, a rung byte per band, the entering values
-        if (i < 6) e0[i] = (uint8_t)(a.idx.bitpos[k] >> (8 * i));
-        else if (i < 6 + B) e0[i] = a.idx.rung[k * B + (i - 6)];
-        else e0[i] = ((const uint8_t *)a.idx.prev)[k * B * tsz + (i - 6 - B)];
-    }
+    ix_blw_fill(ix_fill_of(a), (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, tpe);
 }
-
-// Common-factor streams of the lane-per-unit decoder (k_dec_pxu.hip): a three-byte field per UNIT of the entry's segment -- its bits (12)
-// | the rung it is entered with << 12 -- from the index's unit table; a thread per four units, sixteen threads an entry (a segment is at
-// most 64 units), which also share the entry's fixed part
+// common-factor streams of the lane-per-unit decoder: a three-byte field per unit, a thread per four units
 __global__ void __launch_bounds__(256) ix_blu_best_fill_kernel(const EncArgs a0) {
     const EncArgs a = enc_for_tile(a0, blockIdx.y);
-    const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t B = a.g.bands, tsz = a.g.tsz, upe = a.ix_blocks * B;         // units per entry
-    const uint64_t k = idx >> 4;
-    if (k >= a.ix_K) return;
-    const uint32_t t = (uint32_t)(idx & 15);
-    const uint64_t u0 = k * upe, nunits = a.g.nblocks * B;
-    const uint32_t c = (uint32_t)(k / a.ix_per_chunk), jj = (uint32_t)(k - (uint64_t)c * a.ix_per_chunk);
-    uint8_t *e0 = a.ix_dst + (uint64_t)c * (IX_HEAD + IX_PAD + (uint64_t)a.ix_per_chunk * a.ix_E) + IX_HEAD + (uint64_t)jj * a.ix_E;
-    const uint32_t fixed = 6 + B * (1 + 2 * tsz);
-    if (4 * t + 4 <= upe) {     // four whole fields: three dwords
-        uint32_t fl[4];
-#pragma unroll
-        for (uint32_t q = 0; q < 4; q++) {
-            const uint32_t f = 4 * t + q;
-            const uint32_t bt = u0 + f < nunits ? ((const uint32_t *)a.idx.ulen)[u0 + f] : 0u;
-            fl[q] = (bt & 0xfffu) | ((bt >> 16) & 63u) << 12;
-        }
-        ix_store12(e0 + fixed + IX_BL_BEST_BYTES * 4 * t, fl);
-    } else
-        for (uint32_t q = 0; q < 4; q++) {
-            const uint32_t f = 4 * t + q;
-            if (f >= upe) break;
-            const uint32_t bt = u0 + f < nunits ? ((const uint32_t *)a.idx.ulen)[u0 + f] : 0u;
-            const uint32_t fld = (bt & 0xfffu) | ((bt >> 16) & 63u) << 12;
-            uint8_t *e = e0 + fixed + IX_BL_BEST_BYTES * f;
-            e[0] = (uint8_t)fld; e[1] = (uint8_t)(fld >> 8); e[2] = (uint8_t)(fld >> 16);
-        }
-    for (uint32_t i = t; i < fixed; i += 16) {
-        uint8_t v;
-        if (i < 6) v = (uint8_t)(a.idx.bitpos[k] >> (8 * i));
-        else if (i < 6 + B) v = a.idx.rung[k * B + (i - 6)];
-        else if (i < 6 + B + B * tsz) v = ((const uint8_t *)a.idx.prev)[k * B * tsz + (i - 6 - B)];
-        else v = ((const uint8_t *)a.idx.cf)[k * B * tsz + (i - 6 - B - B * tsz)];
-        e0[i] = v;
-    }
+    ix_blu_best_fill(ix_fill_of(a), (uint64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // The last word on the table: every chunk's 16-bit check of its entries into the head's reserved bytes (ix_sum_part)
 __global__ void __launch_bounds__(256) ix_seal_kernel(const EncArgs a0) {
     const EncArgs a = enc_for_tile(a0, blockIdx.y);
     __shared__ uint32_t part[4];
+    const IxFill f = ix_fill_of(a);
     const uint32_t c = blockIdx.x;
-    const uint32_t here = (a.ix_K - c * a.ix_per_chunk < a.ix_per_chunk) ? a.ix_K - c * a.ix_per_chunk : a.ix_per_chunk;
-    uint8_t *chunk = a.ix_dst + (uint64_t)c * (IX_HEAD + IX_PAD + (uint64_t)a.ix_per_chunk * a.ix_E);
-    uint32_t s = ix_sum_part(chunk + IX_HEAD, here * a.ix_E, threadIdx.x, 256);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += (uint32_t)__shfl_xor((int)s, d, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
+    const uint32_t check = ix_chunk_check(f, c, part);
     if (threadIdx.x == 0) {
-        const uint32_t f = ix_sum_fold(part[0] + part[1] + part[2] + part[3]);
-        chunk[6] = (uint8_t)f; chunk[7] = (uint8_t)(f >> 8);
+        uint8_t *chunk = ix_chunk_ptr(f, c);
+        chunk[6] = (uint8_t)check; chunk[7] = (uint8_t)(check >> 8);
     }
 }
 

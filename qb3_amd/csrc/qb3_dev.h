@@ -272,6 +272,16 @@ int launch_decode_windows(const Geometry &g, const DecPlan &plan, const uint32_t
                           const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
                           uint32_t *d_status, void *stream, const IxTable &ix);
 
+// Reindex (k_reindex.hip): the table chunks this library's encoder writes for a raster, made from the index a plain walk of its stream
+// has rebuilt (launch_decode with index == nullptr leaves it in ws behind the status words), and the new container around them.
+// launch_reindex_fill writes the entries of the table laid out by ix (ix.base: where its first chunk goes) from the index at `index`.
+// launch_reindex_finish, in one launch: hdr_len header bytes from HOST memory at hdr to d_dst (when there is no table they end with "DT");
+// every chunk's head, pad and check and the "DT" behind the last (ix.K == 0: no table); the n coded bytes at d_src to d_pay, which
+// may stand at any byte distance from each other.  Neither synchronises.  Both return hipError_t as int.
+int launch_reindex_fill(const Geometry &g, void *index, const IxTable &ix, void *stream);
+int launch_reindex_finish(const Geometry &g, const IxTable &ix, const uint8_t *hdr, size_t hdr_len, void *d_dst, const void *d_src, void *d_pay, uint64_t n, void *stream);
+constexpr size_t DEC_WS_INDEX_OFF = 64;     // a single image's rebuilt index in the decoder's workspace: behind the status words
+
 // The RLE0 byte pass of the *_RLE modes on device buffers (k_rle0.hip; reference QB3encode.cpp:271-332, QB3decode.cpp:267-307).
 // ws: rle0_ws_bytes(n) bytes of device memory.  rle0_device_size returns the size of the coded (decode = false) or
 // expanded (decode = true) form and synchronises the stream; rle0_device_write, called next with the same arguments,

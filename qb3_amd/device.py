@@ -148,6 +148,22 @@ class DeviceDecoder:
             raise RuntimeError(f"qb3x_decode_windows_device wrote {n} of {len(rects)} windows: {last_error()}")
         return [o.view(-1)[:nb].view(getattr(torch, NP_DTYPE[dt])).view(h, w, self.bands) for o, nb, (_, _, w, h) in zip(out, sizes, rects)]
 
+    def reindex(self, d_stream, level, out=None):
+        """the container with the restart table this library's encoder writes at `level` (0: none), its coded bytes untouched
+        (qb3x_reindex_device).  The decoder must have been made over a host copy of the WHOLE container.  out: a contiguous uint8
+        device tensor of at least qb3x_reindex_size bytes that does not overlap d_stream.  Returns (tensor, nbytes)."""
+        assert d_stream.is_cuda
+        cap = lib.qb3x_reindex_size(self.p, level)
+        if not cap:
+            raise ValueError("qb3x_reindex_size refused the handle (made over the container's head only?) or the level")
+        if out is None:
+            out = torch.empty((cap + 3) // 4 * 4, dtype=torch.uint8, device=d_stream.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8 and out.numel() >= cap
+        n = lib.qb3x_reindex_device(self.p, _vp(d_stream.data_ptr()), _vp(out.data_ptr()), out.numel(), level, _stream_ptr())
+        if n == 0:
+            raise RuntimeError(f"qb3x_reindex_device failed (status {lib.qb3x_last_decode_status(self.p)}): {last_error()}")
+        return out, n
+
     @property
     def last_windows(self):
         """the paths of the last decode_windows, one a window (0: not written; 1, 2, 3 as last_window)"""
