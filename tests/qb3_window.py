@@ -56,6 +56,6 @@ def open_handle(L, buf):
 
 
 def handle_error(p):
-    """the decoder handle's error word: the handle starts with four size_t, two uint64 and `int error` (qb3_api.cpp, struct decs,
+    """the decoder handle's error word: the handle starts with four size_t, two uint64 and `int error` (qb3_host.h, struct decs,
     the reference's layout QB3decode.h:36-49); there is no getter in the reference's interface"""
     return C.c_int.from_address(p + 48).value
