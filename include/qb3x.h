@@ -130,6 +130,54 @@ size_t qb3x_read_windows(decsp p, const qb3x_window *wins, size_t n);
 int    qb3x_window_ok(const decsp p, size_t i);     /* 1: window i of the last batch call was written */
 int    qb3x_window_path(const decsp p, size_t i);   /* 0 failed, 1 / 2 / 3 as qb3x_last_window_path */
 
+/* Ranged window reads: windows of a container the caller does NOT hold in memory -- a file, an object in a store -- fetching only the
+ * bytes that hold the rectangles.  The caller gives a reader: rd(ctx, offset, dst, size) copies `size` container bytes from `offset`
+ * to dst (host memory) and returns 0, or nonzero on failure; it is called from the calling thread only, one call at a time, and never
+ * for bytes outside [0, container_size).  No counterpart in the reference, whose containers are in host memory (QB3.h:133-141).
+ * qb3x_open_ranged: what qb3x_read_start_device does, with rd in place of the device-to-host copies: a handle past qb3_read_info that
+ * owns its copy of the container's head and remembers rd / ctx (both must outlive it).  It reads the first bytes chunk head by chunk
+ * head, steps over a regular run of "ix" / "zz" chunks arithmetically and reads the "DT" mark behind it: never an entry of the table,
+ * never the stream (a table that is not regular is read whole, as qb3x_read_start_device reads it).  NULL: rd failed, or not a container.
+ * qb3x_read_windows_ranged (host destinations) and qb3x_decode_windows_ranged (device destinations): bytes, errors, dequantisation,
+ * per-window results (qb3x_window_ok, qb3x_window_path, qb3x_last_window_path, qb3x_last_window_segments) are those of
+ * qb3x_read_windows / qb3x_decode_windows_device over the whole container: the crop of the whole decode, no byte outside a window's
+ * rows, one bad rectangle refuses the batch (QB3E_EINV) before rd is called.  A handle that is not qb3x_open_ranged's: QB3E_EINV.
+ * The shortcut is taken where path 1 is -- 8-bit, 1 / 3 / 4 bands, FTL / BASE, a level-2 table of version 3 -- and what it reads is
+ * fixed by these rules, so that qb3x_ranged_bytes is a number the caller can compute beforehand:
+ *   table chunks   With S0 / S1 the first / last index segment that holds a block of window i (qb3x_window_segments' rule), K the
+ *                  table's entries and N its entries per chunk: the chunks S0 / N .. min(S1 + 1, K - 1) / N of every window, and
+ *                  always the table's last chunk (K - 1) / N; each once.  Chunk c is the container's bytes from T + c * (16 + N * E),
+ *                  T the offset of the first "ix" chunk and E the entry size: 12 + n * E + 4 of them (head, its n entries, the pad),
+ *                  and 2 more for the last chunk (the "DT" mark).  A chunk is read whole, in one call of rd, unless the handle's
+ *                  cache holds it (qb3x_set_ranged_cache: verified chunks, 64 MB by default, the oldest leave first; 0: none).
+ *                  Head, pad, mark and the 16-bit check of every chunk read are verified on the host (the formula above), and the
+ *                  table's last entry must not lie beyond the stream's end.
+ *   pieces         Every block row of every window needs a run of consecutive segments s0 .. s1; with P(s) the 6-byte position of
+ *                  entry s (P(K): the stream's length in bits) and D the offset of the first stream byte, the run's bytes are
+ *                  [D + P(s0) / 8, D + (P(s1 + 1) + 7) / 8), widened to container offsets that are multiples of 4 and clipped to
+ *                  the container's size.  The ranges of all runs of all windows are sorted and merged where they overlap, touch, or
+ *                  lie at most `gap` bytes apart (qb3x_set_ranged_gap; 0 by default); every merged range is one call of rd.
+ * qb3x_ranged_bytes / qb3x_ranged_reads: the bytes and the calls the handle's last ranged call asked of rd.
+ * The pieces go up packed back to back, with the entries their segments use and a sorted piece list, and ONE launch decodes every
+ * window from them (profile name dec_window_ranged); the kernel reads no word outside a segment's piece, whatever the entries say.
+ * Falling back costs time and bytes, never pixels: a chunk or the table's end failing its check, pieces whose window ends with a
+ * nonzero status, a raster the shortcut does not take, a container without a usable table -- the call reads the WHOLE container
+ * through rd, once, and goes the way of qb3x_read_windows / qb3x_decode_windows_device for the windows that have no pixels yet.
+ * STORED containers need no device and no table: the windows' rows, and only them, are read from their offsets (a call of rd per row
+ * of a window; one for a window as wide as the raster).  An rd that returns nonzero fails the call (QB3E_ERR, 0 returned).
+ * qb3x_ranged_table_ranges: pure planning, no device and no rd: the chunk ranges above for a batch, sorted, cached or not; returns
+ * their count and writes the first `cap` to out (which may be NULL); 0 where the shortcut does not apply or a rectangle is bad. */
+typedef int (*qb3x_read_fn)(void *ctx, uint64_t offset, void *dst, size_t size);
+typedef struct { uint64_t offset, size; } qb3x_range;
+decsp  qb3x_open_ranged(qb3x_read_fn rd, void *ctx, uint64_t container_size, size_t *image_size);
+size_t qb3x_read_windows_ranged(decsp p, const qb3x_window *wins, size_t n);
+size_t qb3x_decode_windows_ranged(decsp p, const qb3x_window *wins, size_t n, void *stream);
+uint64_t qb3x_ranged_bytes(const decsp p);
+uint64_t qb3x_ranged_reads(const decsp p);
+void   qb3x_set_ranged_gap(decsp p, size_t bytes);
+void   qb3x_set_ranged_cache(decsp p, size_t bytes);
+size_t qb3x_ranged_table_ranges(const decsp p, const qb3x_window *wins, size_t n, qb3x_range *out, size_t cap);
+
 /* Batched tiles: n images of the encoder's geometry, image i at d_src + i*src_pitch, container i
  * written at d_dst + i*dst_pitch (dst_pitch >= qb3_max_encoded_size, multiple of 4), index i at
  * d_index + i*qb3x_index_size (or NULL).  sizes[i] receives the container size (0 = failed).
@@ -265,7 +313,7 @@ size_t qb3_decode(decsp p, void *destination);                                  
  * events on the launch stream; totals are resolved at the library's own synchronisation points.
  * Kernel names: enc_units, enc_scan, enc_concat, enc_seams, enc_best_units, enc_best_scan, enc_best_recode,
  * dec_index_table, dec_index_serial, dec_index_prev, dec_index_scan, dec_units, dec_segments, dec_window (the window kernel of
- * qb3x_decode_window_device, path 1), reindex_fill, reindex_finish (qb3x_reindex_device: the table's entries; everything else of the
+ * qb3x_decode_window_device, path 1), dec_window_ranged (the same from fetched pieces: the ranged calls), reindex_fill, reindex_finish (qb3x_reindex_device: the table's entries; everything else of the
  * new container).
  * level: 0 off, 1 every kernel, 2 all but the microsecond kernels (enc_scan, enc_seams, enc_best_scan), whose two
  * events cost more than they take. */

@@ -49,6 +49,14 @@ def window_array(rects, ptrs, strides=None):
     return arr
 
 
+class Range(C.Structure):
+    """qb3x_range (include/qb3x.h): a byte range of a container"""
+    _fields_ = [("offset", _u64), ("size", _u64)]
+
+
+READ_FN = C.CFUNCTYPE(C.c_int, _vp, _u64, _vp, _sz)     # qb3x_read_fn: 0 = ok
+
+
 _PROTOS = {
     # name: (restype, argtypes)            -- include/QB3.h
     "qb3_create_encoder": (_vp, [_sz, _sz, _sz, C.c_int]),
@@ -93,6 +101,14 @@ _PROTOS = {
     "qb3x_read_windows": (_sz, [_vp, _vp, _sz]),
     "qb3x_window_ok": (C.c_int, [_vp, _sz]),
     "qb3x_window_path": (C.c_int, [_vp, _sz]),
+    "qb3x_open_ranged": (_vp, [_vp, _vp, _u64, C.POINTER(_sz)]),
+    "qb3x_read_windows_ranged": (_sz, [_vp, _vp, _sz]),
+    "qb3x_decode_windows_ranged": (_sz, [_vp, _vp, _sz, _vp]),
+    "qb3x_ranged_bytes": (_u64, [_vp]),
+    "qb3x_ranged_reads": (_u64, [_vp]),
+    "qb3x_set_ranged_gap": (None, [_vp, _sz]),
+    "qb3x_set_ranged_cache": (None, [_vp, _sz]),
+    "qb3x_ranged_table_ranges": (_sz, [_vp, _vp, _sz, _vp, _sz]),
     "qb3x_read_start": (_vp, [_vp, _sz, _sz, C.POINTER(_sz)]),
     "qb3x_read_start_device": (_vp, [_vp, _sz, C.POINTER(_sz), _vp]),
     "qb3x_header_size_bound": (_sz, [_vp, _sz]),
@@ -258,3 +274,85 @@ def reindex(stream, level):
     if n == 0:
         raise RuntimeError(f"qb3x_reindex failed: {last_error()}")
     return out[:n]
+
+
+class RangedReader:
+    """qb3x_open_ranged: windows of a container that is NOT in memory -- a file, or anything a callable reads byte ranges of --
+    fetching only the table chunks and the pieces of the stream that hold the rectangles (include/qb3x.h).  `source`: a path, or a
+    callable (offset, size) -> bytes-like of exactly `size` bytes (then `size` is the container's size).  last_bytes / last_reads:
+    what the last call asked of the source; last_windows: the path every window of it came by."""
+
+    def __init__(self, source, size=None):
+        import numpy as np
+        self._file = None
+        if callable(source):
+            if size is None:
+                raise ValueError("a callable source needs the container's size")
+            read = source
+        else:
+            self._file = open(source, "rb")
+            size = os.fstat(self._file.fileno()).st_size if size is None else size
+            fd = self._file.fileno()
+            read = lambda off, n: os.pread(fd, n, off)  # noqa: E731
+
+        def rd(_ctx, off, dst, n):
+            try:
+                got = np.frombuffer(read(off, n), np.uint8)
+                if got.size != n:
+                    return 1
+                C.memmove(dst, got.ctypes.data, n)
+                return 0
+            except Exception:       # (no exception crosses the C ABI)
+                return 1
+        self._rd = READ_FN(rd)      # referenced for the handle's life: the library calls it until close()
+        self.size = int(size)
+        dims = (_sz * 3)()
+        self.p = lib.qb3x_open_ranged(self._rd, None, self.size, dims)
+        if not self.p:
+            self.close()
+            raise ValueError("qb3x_open_ranged: not a QB3 container, or the source could not be read")
+        self.width, self.height, self.bands = (int(v) for v in dims)
+        self.dtype = lib.qb3_get_type(self.p)
+        self.last_bytes = self.last_reads = 0
+        self.last_windows = []
+
+    def set_gap(self, nbytes):
+        lib.qb3x_set_ranged_gap(self.p, nbytes)
+
+    def set_cache(self, nbytes):
+        lib.qb3x_set_ranged_cache(self.p, nbytes)
+
+    def _after(self, n):
+        self.last_bytes, self.last_reads = lib.qb3x_ranged_bytes(self.p), lib.qb3x_ranged_reads(self.p)
+        self.last_windows = [lib.qb3x_window_path(self.p, i) for i in range(n)]
+
+    def read_windows(self, rects):
+        """qb3x_read_windows_ranged: the windows (x0, y0, w, h) as a list of arrays of shape (h, w, bands)"""
+        import numpy as np
+        rects = [tuple(int(v) for v in r) for r in rects]
+        outs = [np.empty((h, w, self.bands), dtype=NP_DTYPE[self.dtype]) for _, _, w, h in rects]
+        wins = window_array(rects, [o.ctypes.data for o in outs])
+        n = lib.qb3x_read_windows_ranged(self.p, wins, len(rects))
+        self._after(len(rects))
+        if n != len(rects):
+            raise RuntimeError(f"qb3x_read_windows_ranged wrote {n} of {len(rects)} windows: {last_error()}")
+        return outs
+
+    def close(self):
+        if getattr(self, "p", None):
+            lib.qb3_destroy_decoder(self.p)
+        self.p = None
+        if self._file is not None:
+            self._file.close()
+            self._file = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def open_ranged(path_or_callable, size=None):
+    """a RangedReader over a file or a callable (offset, size) -> bytes"""
+    return RangedReader(path_or_callable, size)

@@ -26,7 +26,7 @@ static bool window_check(const decs *p, const qb3x_window &w) {
     return w.dst && window_inside(p, w.x0, w.y0, w.w, w.h) && (!w.dst_stride || w.dst_stride >= w.w * p->nbands);
 }
 // handle and rectangles of a window call (host: the container is read from the handle's host memory); false: p->error is set, nothing was touched
-static bool windows_check(decsp p, const qb3x_window *wins, size_t n, bool host) {
+bool qb3api::windows_check(decsp p, const qb3x_window *wins, size_t n, bool host) {
     if (p->stage != 2 || p->error != QB3E_OK || p->s_in == nullptr || p->s_size == 0) {
         if (p->error == QB3E_OK) p->error = QB3E_EINV;
         return false;
@@ -125,7 +125,7 @@ static bool window_strips(decsp p, const WinSrc &s, const qb3x_window *wins, siz
 
 // The windows of a container in device memory into their device buffers.  paths: a zeroed byte per window, which receives the path the
 // window's pixels came by (0: none); single: one of the single calls.  Returns the number of windows written.
-static size_t windows_device(decsp p, const void *d_src, const void *d_index, const qb3x_window *wins, size_t n, uint8_t *paths, bool single, hipStream_t st) {
+size_t qb3api::windows_device(decsp p, const void *d_src, const void *d_index, const qb3x_window *wins, size_t n, uint8_t *paths, bool single, hipStream_t st) {
     const bool coded = p->mode != QB3M_STORED && p->xsize >= 4 && p->ysize >= 4;       // (narrow images decode through a stand-in shape: no block grid)
     p->win_path = 0; p->win_segs = 0;
     Geometry g;
@@ -178,7 +178,7 @@ static size_t windows_device(decsp p, const void *d_src, const void *d_index, co
 // The same for a container in host memory and host destinations (paths, single: as above): STORED containers are cropped on the
 // host; else the whole container goes up ONCE (the stream and its table), the windows are decoded back to back into one device
 // buffer (each starts on a dword) and come down one by one, each with its stride
-static size_t windows_host(decsp p, const qb3x_window *wins, size_t n, uint8_t *paths, bool single) {
+size_t qb3api::windows_host(decsp p, const qb3x_window *wins, size_t n, uint8_t *paths, bool single) {
     const size_t tsz = szof(p->type), pix = p->nbands * tsz, line = p->xsize * pix, csize = (size_t)(p->s_in - p->s_start) + p->s_size;
     p->win_path = 0; p->win_segs = 0;
     if (p->mode == QB3M_STORED) {           // raw pixels: no device needed (reference QB3decode.cpp:356-375)

@@ -271,6 +271,17 @@ size_t window_batch_plan(const Geometry &g, const IxTable &ix, const WinRect *re
 int launch_decode_windows(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
                           const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
                           uint32_t *d_status, void *stream, const IxTable &ix);
+// The same from PIECES of the container (k_dec_wins_ranged.hip; api_ranged.cpp fetches them): d_pieces: npieces >= 1 pieces sorted by
+// first segment, each a run of consecutive segments { seg0, nseg, ent0, word0, stream word of its first packed word (low, high),
+// nwords, 0 }; d_entries: the compact array of table entries (ix.entry_bytes each), nseg + 1 per piece from index ent0; d_words: the
+// pieces' stream words from index word0, counted as launch_decode's in32 counts them (word 0 holds the bit in_bit0 names).  The caller
+// vouches that ent0 + nseg + 1 and word0 + nwords stay inside the two arrays: the kernel reads nothing outside them.  The descriptors
+// are window_batch_plan's; status words as above, word 0 is not written (the table was checked on the host).  ix: the table's shape
+// (its base only has to be non-null).
+constexpr size_t WIN_PIECE_BYTES = 32;
+int launch_decode_windows_ranged(const Geometry &g, const DecPlan &plan, uint32_t in_bit0, uint64_t in_bits, const void *h_descs, const void *d_descs,
+                                 size_t n, const void *d_pieces, size_t npieces, const void *d_entries, const uint32_t *d_words,
+                                 uint32_t *d_status, void *stream, const IxTable &ix);
 
 // Reindex (k_reindex.hip): the table chunks this library's encoder writes for a raster, made from the index a plain walk of its stream
 // has rebuilt (launch_decode with index == nullptr leaves it in ws behind the status words), and the new container around them.

@@ -9,6 +9,7 @@
 #include <exception>
 #include <initializer_list>
 #include <vector>
+#include <utility>
 #include <algorithm>
 #include "../../include/QB3.h"
 #include "../../include/qb3x.h"
@@ -123,6 +124,14 @@ struct decs {
     std::vector<uint8_t> wins_path;                    // ... per window outcome of the last batch call (0: not written, else its path)
     Stager stager, stager2;                            // (stager2: the download ring of a pipelined host call)
     Pipe pipe;                                         // ... its streams and events
+    // a ranged handle (qb3x_open_ranged, api_ranged.cpp): the caller's reader, the container's size, what the last call asked of the reader
+    qb3x_read_fn rg_rd = nullptr;
+    void *rg_ctx = nullptr;
+    uint64_t rg_size = 0, rg_bytes = 0, rg_reads = 0;
+    size_t rg_gap = 0, rg_cache_cap = (size_t)64 << 20, rg_cache_bytes = 0;
+    std::vector<std::pair<uint32_t, std::vector<uint8_t>>> rg_chunks;      // verified table chunks by number, oldest first
+    PinBuf h_rg;                                       // ... pieces, entries, piece list and descriptors as uploaded
+    DevBuf d_rg;
 };
 
 namespace qb3api {
@@ -155,6 +164,12 @@ size_t write_headers(const encs *p, uint8_t *dst, bool with_dt = true);
 decsp read_start_impl(void *source, size_t hdr_avail, size_t source_size, size_t *image_size);
 qb3dev::IxTable handle_table(const decs *p, const uint8_t *base);
 qb3dev::Geometry decoder_geometry(const decs *p, size_t w, size_t h, size_t stride);
+
+// api_window.cpp: handle and rectangles of a window call (false: p->error is set); the windows of a container in device / host memory
+// (paths: a zeroed byte per window, which receives the path its pixels came by)
+bool windows_check(decsp p, const qb3x_window *wins, size_t n, bool host);
+size_t windows_device(decsp p, const void *d_src, const void *d_index, const qb3x_window *wins, size_t n, uint8_t *paths, bool single, hipStream_t st);
+size_t windows_host(decsp p, const qb3x_window *wins, size_t n, uint8_t *paths, bool single);
 
 // qb3_api.cpp
 qb3dev::Geometry make_geometry(size_t w, size_t h, size_t bands, int dtype, size_t stride, uint64_t order, int mode,

@@ -44,11 +44,63 @@ __device__ __forceinline__ void ix_tail_check(const DecArgs &a) {
     if (v > a.in_bits) atomicOr(a.status, 4u);
 }
 
+// Where a wave's table entries and stream words come from: a SOURCE POLICY, the one thing the window kernels differ in.
+//   find(seg, wanted)   wave uniform, before any entry is read: true when the source holds segment seg (wanted: the wave is live);
+//   entry(a, k)         entry k of the table, for k = seg and seg + 1 of a segment find() said yes to (and for segment 0 of any wave);
+//   holds(w0, ndw)      are the stream words [w0, w0 + ndw) (counted from a.in32's word) the source's to read;
+//   word(a, w, endw)    stream word w of a range holds() said yes to; zero at and behind word endw, the container's end.
+// The contiguous source: the whole container in device memory (dec_win_kernel, dec_wins_kernel) -- every segment, every word.
+struct WinSrcContig {
+    __device__ __forceinline__ bool find(uint32_t, bool) { return true; }
+    __device__ __forceinline__ const uint8_t *entry(const DecArgs &a, uint32_t k) const { return ix_entry_at(a.ix, a.ix_per_chunk, a.ix_E, a.ix_pad, k); }
+    __device__ __forceinline__ bool holds(uint64_t, uint64_t) const { return true; }
+    __device__ __forceinline__ uint32_t word(const DecArgs &a, uint64_t w, uint64_t endw) const { return w < endw ? a.in32[w] : 0u; }
+};
+// The ranged source (k_dec_wins_ranged.hip): PIECES of the stream packed back to back, a compact array of the entries their segments
+// use, and a list of the pieces sorted by first segment.  A piece is a run of consecutive segments whose bytes were fetched as one
+// range: eight dwords { first segment, segments, index of its first entry in the compact array (it has segments + 1: the entry behind
+// the run ends it), index of its first word in the packed buffer, the stream word that word is (low, high), words, 0 }.  Nothing is
+// read outside the piece and the piece's entries, whatever the entries say: a segment that is not wholly inside its piece does not
+// "hold" and stages zeros, as one that exceeds the staging area does.
+struct WinPiece { uint32_t seg0, nseg, ent0, word0, sw0_lo, sw0_hi, nwords, pad_; };
+static_assert(sizeof(WinPiece) == 32, "WinPiece is read with scalar loads of eight dwords");
+struct WinSrcPieces {
+    const WinPiece *pieces;         // npieces >= 1 of them, seg0 growing strictly
+    const uint8_t *ents;            // the compact array, entries of a.ix_E bytes
+    const uint32_t *words;          // the packed pieces
+    uint32_t npieces;
+    WinPiece pc;                    // the wave's piece (after find)
+    __device__ __forceinline__ bool find(uint32_t seg, bool wanted) {
+        // the last piece whose first segment is not behind seg: wave uniform, as the window search of k_dec_wins.hip
+        uint32_t lo = 0, hi = npieces;
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (pieces[mid].seg0 <= seg) lo = mid; else hi = mid;
+        }
+        lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
+        pc = pieces[lo];
+        const bool in = seg >= pc.seg0 && seg - pc.seg0 < pc.nseg;
+        if (!in) { pc = pieces[0]; pc.nwords = 0; }      // (entry() then gives the array's first two entries: inside it, never used)
+        return in || !wanted;
+    }
+    __device__ __forceinline__ const uint8_t *entry(const DecArgs &a, uint32_t k) const {
+        const uint32_t j = k - pc.seg0;                 // 0 .. nseg for a segment of the piece
+        return ents + (uint64_t)(pc.ent0 + (j <= pc.nseg ? j : 0u)) * a.ix_E;
+    }
+    __device__ __forceinline__ bool holds(uint64_t w0, uint64_t ndw) const {
+        const uint64_t sw0 = (uint64_t)pc.sw0_hi << 32 | pc.sw0_lo;
+        return w0 >= sw0 && w0 - sw0 <= pc.nwords && ndw <= pc.nwords - (w0 - sw0);
+    }
+    __device__ __forceinline__ uint32_t word(const DecArgs &, uint64_t w, uint64_t) const {
+        return words[pc.word0 + (uint32_t)(w - ((uint64_t)pc.sw0_hi << 32 | pc.sw0_lo))];      // (behind the container's end a piece has no words: holds() said no)
+    }
+};
+
 // Wave `wid` of window w (wave: its number in the workgroup of four; both wave uniform): the k-th segment of one of the window's block
 // rows, decoded as dec_px_kernel's BL branch does, stored where the window's blocks go.  status: the word this window's failures go to.
 // Every wave of the workgroup comes here (there is one workgroup barrier); smem: the launch's dynamic LDS, at LDS address 0.
-template <int B, bool RGB, uint64_t ORDER, bool STEP>
-__device__ __forceinline__ void win_decode_wave(const DecArgs &a, const WinDesc &w, uint32_t *status, uint8_t *smem, uint32_t wave, uint32_t wid) {
+template <int B, bool RGB, uint64_t ORDER, bool STEP, class SRC = WinSrcContig>
+__device__ __forceinline__ void win_decode_wave(const DecArgs &a, const WinDesc &w, uint32_t *status, uint8_t *smem, uint32_t wave, uint32_t wid, SRC src = SRC()) {
     constexpr int NW = (B + 1) / 2;                     // 32-bit words of a scan packed 16 bits per band
     constexpr uint32_t NB = 64;                         // blocks of a segment
     const uint32_t tid = threadIdx.x, lane = tid & 63;
@@ -64,6 +116,8 @@ __device__ __forceinline__ void win_decode_wave(const DecArgs &a, const WinDesc 
     const uint32_t seg = (row0 + w.bx0) / NB + k;
     bool live = wid < w.nwaves && seg <= (row0 + w.bx1) / NB;
     if (r > 0 && seg <= (row0 - nbx + w.bx1) / NB) live = false;
+    const bool placed = src.find(live ? seg : 0, live);     // (a segment the source does not hold: the wave leaves behind the barrier)
+    live = live && placed;
     const uint32_t segc = live ? seg : 0;
     const uint32_t g0 = segc * NB, nblocks = (uint32_t)a.g.nblocks;
     const uint32_t nb_here = (nblocks - g0 < NB) ? nblocks - g0 : NB;
@@ -71,13 +125,13 @@ __device__ __forceinline__ void win_decode_wave(const DecArgs &a, const WinDesc 
     uint64_t P0, P1;
     uint32_t rg0[B], pv0[B], blen = 0;
     {
-        const uint8_t *e = ix_entry_at(a.ix, a.ix_per_chunk, a.ix_E, a.ix_pad, segc);
+        const uint8_t *e = src.entry(a, segc);
         auto pos6 = [](const uint8_t *q) { uint64_t v = 0;
 #pragma unroll
             for (uint32_t i = 0; i < 6; i++) v |= (uint64_t)q[i] << (8 * i);
             return v; };
         P0 = pos6(e);
-        P1 = ((uint64_t)segc + 1 < a.g.nseg) ? pos6(ix_entry_at(a.ix, a.ix_per_chunk, a.ix_E, a.ix_pad, segc + 1)) : a.in_bits;
+        P1 = ((uint64_t)segc + 1 < a.g.nseg) ? pos6(src.entry(a, segc + 1)) : a.in_bits;
 #pragma unroll
         for (int c = 0; c < B; c++) { rg0[c] = e[6 + c] & 7u; pv0[c] = e[6 + B + c]; }
         const uint8_t *bl = e + 6 + 2 * B + ((IX_BL_BITS * lane) >> 3);
@@ -85,19 +139,22 @@ __device__ __forceinline__ void win_decode_wave(const DecArgs &a, const WinDesc 
     }
     for (uint32_t i = tid; i < 256; i += blockDim.x) ((uint4 *)tab)[i] = ((const uint4 *)px_dec_tab.e)[i];
     __syncthreads();                                    // the only workgroup barrier
-    if (!live) return;
+    if (!live) {
+        if (!placed && lane == 0) atomicOr(status, 8u);
+        return;
+    }
     const uint64_t w0 = (a.in_bit0 + P0) >> 5;
     const uint64_t endw_abs = (a.in_bit0 + a.in_bits + 31) >> 5;
     const uint64_t ndw64 = ((a.in_bit0 + P1 + 31) >> 5) - w0;
     // the staging area holds the longest valid segment; a table that says otherwise is not this stream's
-    const bool fits = ndw64 <= a.in_cap_dw && lds0 == 0;
+    const bool fits = ndw64 <= a.in_cap_dw && lds0 == 0 && src.holds(w0, ndw64);
     const uint32_t ndw = fits ? (uint32_t)ndw64 : 0;
     for (uint32_t base = 0; base < ndw + 8; base += 512) {          // eight loads in flight per lane, then eight LDS stores
         uint32_t sw[8];
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             const uint32_t i = base + lane + 64 * j;
-            sw[j] = (i < ndw && w0 + i < endw_abs) ? a.in32[w0 + i] : 0u;
+            sw[j] = i < ndw ? src.word(a, w0 + i, endw_abs) : 0u;
         }
 #pragma unroll
         for (int j = 0; j < 8; j++) {

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import lib, last_error, TYPESIZE, NP_DTYPE, QB3M_FTL, _sz, window_array
+from . import lib, last_error, TYPESIZE, NP_DTYPE, QB3M_FTL, _sz, window_array, RangedReader
 
 _vp = C.c_void_p
 
@@ -256,3 +256,30 @@ def profile_report():
         if lib.qb3x_profile_get(name.encode(), C.byref(ms), C.byref(cnt)):
             out[name] = (ms.value, cnt.value)
     return out
+
+
+class RangedDecoder(RangedReader):
+    """qb3_amd.open_ranged with device destinations: the container stays where it is (a file, a callable), the windows arrive in
+    device memory (qb3x_decode_windows_ranged)."""
+
+    def decode_windows(self, rects, out=None):
+        """the windows (x0, y0, w, h) of `rects` in one call: a list of device tensors of shape (h, w, bands) and the raster's type.
+        out: as DeviceDecoder.decode_windows."""
+        dt = self.dtype
+        rects = [tuple(int(v) for v in r) for r in rects]
+        sizes = [h * w * self.bands * TYPESIZE[dt] for _, _, w, h in rects]
+        if out is None:                 # one allocation, every window on a dword
+            offs = [0]
+            for nb in sizes:
+                offs.append(offs[-1] + (nb + 3) // 4 * 4)
+            buf = torch.empty(max(offs[-1], 4), dtype=torch.uint8, device="cuda")
+            out = [buf[offs[i]:offs[i] + sizes[i]] for i in range(len(rects))]
+        assert len(out) == len(rects)
+        for o, nb in zip(out, sizes):
+            assert o.is_cuda and o.is_contiguous() and o.dtype == torch.uint8 and o.numel() >= nb
+        wins = window_array(rects, [o.data_ptr() for o in out])
+        n = lib.qb3x_decode_windows_ranged(self.p, wins, len(rects), _stream_ptr())
+        self._after(len(rects))
+        if n != len(rects):
+            raise RuntimeError(f"qb3x_decode_windows_ranged wrote {n} of {len(rects)} windows: {last_error()}")
+        return [o.view(-1)[:nb].view(getattr(torch, NP_DTYPE[dt])).view(h, w, self.bands) for o, nb, (_, _, w, h) in zip(out, sizes, rects)]

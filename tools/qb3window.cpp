@@ -1,0 +1,90 @@
+// tools/qb3window.cpp -- a rectangle of a QB3 file as a PNM image, reading only the bytes of the file that hold it: the command line
+// caller of qb3x_open_ranged / qb3x_read_windows_ranged (include/qb3x.h), with pread as the reader.  A file with a level-2 restart
+// table (cqb3x with QB3X_INDEX_CHUNK=2, qb3index -2) is read in pieces; any other file is read whole and gives the same pixels.
+//
+//   qb3window [-v] [-g gap] in.qb3 x0,y0,w,h out.pnm
+//
+//   -g gap  merge two byte ranges that lie at most `gap` bytes apart (fewer reads, more bytes; default 0)
+//   -v      prints bytes read and calls of the reader against the file's size
+#include "qb3x.h"
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+namespace {
+
+const char *USAGE = "qb3window [-v] [-g gap] in.qb3 x0,y0,w,h out.pnm\n";
+
+int fail(const std::string &msg) {
+    fprintf(stderr, "qb3window: %s\n", msg.c_str());
+    return 1;
+}
+
+// qb3x_read_fn over a file descriptor
+int read_at(void *ctx, uint64_t offset, void *dst, size_t size) {
+    const int fd = *(const int *)ctx;
+    uint8_t *to = (uint8_t *)dst;
+    while (size) {
+        const ssize_t got = pread(fd, to, size, (off_t)offset);
+        if (got <= 0) return 1;
+        to += got; offset += (uint64_t)got; size -= (size_t)got;
+    }
+    return 0;
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    bool verbose = false;
+    size_t gap = 0;
+    std::vector<std::string> names;
+    for (int i = 1; i < argc; i++) {
+        const std::string a = argv[i];
+        if (a == "-v") verbose = true;
+        else if (a == "-g" && i + 1 < argc) gap = (size_t)strtoull(argv[++i], nullptr, 10);
+        else if (!a.empty() && a[0] == '-') { fputs(USAGE, stderr); return 2; }
+        else names.push_back(a);
+    }
+    unsigned long long x0, y0, w, h;
+    if (names.size() != 3 || sscanf(names[1].c_str(), "%llu,%llu,%llu,%llu", &x0, &y0, &w, &h) != 4) { fputs(USAGE, stderr); return 2; }
+    int fd = open(names[0].c_str(), O_RDONLY);
+    struct stat sb;
+    if (fd < 0 || fstat(fd, &sb) != 0) return fail("cannot read " + names[0]);
+    size_t dims[3];
+    decsp d = qb3x_open_ranged(read_at, &fd, (uint64_t)sb.st_size, dims);
+    if (!d) { close(fd); return fail(names[0] + " is not a QB3 container"); }
+    const qb3_dtype type = qb3_get_type(d);
+    const size_t tsz = type <= QB3_I8 ? 1 : type <= QB3_I16 ? 2 : type <= QB3_I32 ? 4 : 8;
+    int ret = 0;
+    if ((dims[2] != 1 && dims[2] != 3) || tsz > 2) ret = fail("a PNM image holds one or three bands of 8 or 16 bits");
+    else if (!w || !h || x0 >= dims[0] || w > dims[0] - x0 || y0 >= dims[1] || h > dims[1] - y0) ret = fail("the window is not inside the raster");
+    else {
+        std::vector<uint8_t> pix(w * h * dims[2] * tsz);
+        const qb3x_window win = { (size_t)x0, (size_t)y0, (size_t)w, (size_t)h, pix.data(), 0 };
+        qb3x_set_ranged_gap(d, gap);
+        if (qb3x_read_windows_ranged(d, &win, 1) != 1) ret = fail(std::string("the window was not read: ") + qb3x_last_error());
+        else {
+            if (tsz == 2) for (size_t i = 0; i + 1 < pix.size(); i += 2) std::swap(pix[i], pix[i + 1]);     // PNM samples are big endian
+            FILE *f = fopen(names[2].c_str(), "wb");
+            bool ok = f != nullptr;
+            if (ok) {
+                fprintf(f, "P%d\n%llu %llu\n%d\n", dims[2] == 1 ? 5 : 6, w, h, tsz == 1 ? 255 : 65535);
+                ok = fwrite(pix.data(), 1, pix.size(), f) == pix.size();
+                ok = fclose(f) == 0 && ok;
+            }
+            if (!ok) ret = fail("cannot write " + names[2]);
+            else if (verbose)
+                printf("%zu x %zu x %zu: window %llu,%llu,%llu,%llu on path %d: %llu bytes in %llu reads of %lld (%.2f %%)\n", dims[0], dims[1], dims[2], x0, y0, w, h,
+                       qb3x_last_window_path(d), (unsigned long long)qb3x_ranged_bytes(d), (unsigned long long)qb3x_ranged_reads(d), (long long)sb.st_size,
+                       100.0 * (double)qb3x_ranged_bytes(d) / (double)sb.st_size);
+        }
+    }
+    qb3_destroy_decoder(d);
+    close(fd);
+    return ret;
+}

@@ -10,7 +10,12 @@ tools/window_bench.py --batch [CASE] -- the batch call (qb3x_decode_windows_devi
 the same handle: 64 windows of 256^2 and 64 of 1024^2 of the headline raster at seeded random origins that are not multiples of 256
 (path 1: one launch against 64), and 16 windows of 256^2 of a plain 4096 x 4096 x 3 container (path 3: one whole decode against
 16).  Same timing: events on the caller's stream, alternating over three rounds in one process, dec_window's time in a pass of its
-own.  One JSON line per case."""
+own.  One JSON line per case.
+
+tools/window_bench.py --ranged FILE [x0,y0,w,h] -- a window of a file on disk read in pieces (qb3x_open_ranged over os.pread,
+qb3x_read_windows_ranged) against qb3x_read_window of the same file read whole: wall-clock milliseconds (the reads are part of the
+work) of a cold window (a fresh handle a call), a warm one (the table chunks cached in the handle) and the whole-file way, the best of
+a few, with the bytes read beside each.  The window defaults to 512 x 512 in the raster's middle.  One JSON line."""
 import json
 import os
 import subprocess
@@ -137,9 +142,55 @@ def run_batch(case):
                       "ratio": round(min(t_batch) / min(t_single), 4), "kernel_ms": kern, "launches_per_call": launches}), flush=True)
 
 
+def run_ranged(path, rect=None):
+    import time
+    import numpy as np
+    import qb3_amd
+    size = os.path.getsize(path)
+    with qb3_amd.open_ranged(path) as rd:
+        W, H = rd.width, rd.height
+    if rect is None:
+        w, h = min(512, W), min(512, H)
+        rect = ((W - w) // 2, (H - h) // 2, w, h)
+
+    def wall(fn, n=5):
+        best, out = None, None
+        for _ in range(n):
+            t0 = time.perf_counter()
+            out = fn()
+            t = (time.perf_counter() - t0) * 1e3
+            best = t if best is None or t < best else best
+        return best, out
+
+    def cold():
+        with qb3_amd.open_ranged(path) as rd:
+            return rd.read_windows([rect])[0], rd.last_bytes, rd.last_reads, rd.last_windows[0]
+
+    def whole():
+        return qb3_amd.decode_window(np.fromfile(path, np.uint8), *rect)
+
+    whole()                                             # (the device and the library's buffers are up before anything is timed)
+    t_whole, want = wall(whole)
+    t_cold, (got, cold_bytes, cold_reads, path1) = wall(cold)
+    assert np.array_equal(got, want), "the ranged window is not the window of the whole file"
+    with qb3_amd.open_ranged(path) as rd:
+        rd.read_windows([rect])
+        t_warm, got = wall(lambda: rd.read_windows([rect])[0])
+        warm_bytes, warm_reads = rd.last_bytes, rd.last_reads
+    assert np.array_equal(got, want)
+    print(json.dumps({"file": os.path.basename(path), "file_bytes": size, "raster": [W, H], "window": list(rect), "path": path1,
+                      "cold_ms": round(t_cold, 3), "cold_bytes": cold_bytes, "cold_reads": cold_reads,
+                      "warm_ms": round(t_warm, 3), "warm_bytes": warm_bytes, "warm_reads": warm_reads,
+                      "whole_file_ms": round(t_whole, 3), "whole_file_bytes": size}), flush=True)
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
-    if args and args[0] == "--batch":
+    if args and args[0] == "--ranged":
+        if len(args) < 2:
+            sys.exit("window_bench: --ranged takes a file (and, optionally, x0,y0,w,h)")
+        run_ranged(args[1], tuple(int(v) for v in args[2].split(",")) if len(args) > 2 else None)
+    elif args and args[0] == "--batch":
         if len(args) > 1:
             run_batch(args[1])
         else:
