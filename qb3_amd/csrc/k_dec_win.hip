@@ -71,8 +71,7 @@ uint64_t window_segments(const Geometry &g, const WinRect &r) {
 }
 
 bool decode_window_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix) {
-    return decode_strips_ok(g, plan, ix) && g.mode != CM_BEST && g.tsz == 1 && plan.px && g.seg_blocks == 64 &&
-           (g.order == HILBERT || g.order == ZCURVE) && g.nblocks < (1ull << 31);
+    return decode_strips_ok(g, plan, ix) && aligned_dec_kernel(g, plan) == DecKernel::px && g.seg_blocks == 64 && g.nblocks < (1ull << 31);
 }
 
 void window_dec_args(DecArgs &a, const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,

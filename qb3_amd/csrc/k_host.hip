@@ -1,4 +1,4 @@
-// qb3_amd/csrc/k_host.hip -- host side of the kernels: plans, workspace layout, launch orchestration, profiling, small elementwise kernels
+// qb3_amd/csrc/k_host.hip -- host side of the kernels: plans, workspace layout, the encoder's launch orchestration (the decoder's: k_dec_launch.hip), profiling, small elementwise kernels
 #include "qb3_kernels.h"
 #include "qb3_walk.h"
 
@@ -190,7 +190,6 @@ IxTable ix_layout(const Geometry &g, int level) {
 }
 uint32_t ulen_size_for(uint32_t tsz, uint32_t mode, uint32_t bands) { return mode == CM_BEST ? (best_block_table(tsz, mode, bands) ? 4 : ULEN_UNIT) : (tsz == 1 ? 1 : 2); }
 
-static size_t align8(size_t v) { return (v + 7) & ~(size_t)7; }
 size_t index_bytes(const Geometry &g) {
     const size_t n = (size_t)g.nseg * g.bands;
     return align8(8 * (size_t)g.nseg) + 2 * align8(n * g.tsz) + align8(n) + align8(ulen_table_bytes(g));
@@ -440,7 +439,7 @@ int launch_encode_tail(const Geometry &g, const EncPlan &plan, const void *img, 
 // LDS dwords per decoder lane: 16*bands values + 2*bands state values + bands rung bytes.  The count is made
 // odd (conflict-free lane stride) for <= 4 byte values; 8-byte values need an 8-byte aligned lane base, so
 // there it is made 2 mod 4.
-static uint32_t dec_lane_dwords(const Geometry &g) {
+uint32_t dec_lane_dwords(const Geometry &g) {
     uint32_t dw = (uint32_t)((16 * g.bands * g.tsz + 2 * g.bands * g.tsz + g.bands + 3) / 4);
     if (g.tsz == 8) { dw = (dw + 1) & ~1u; if ((dw & 3) == 0) dw += 2; }
     else dw |= 1;
@@ -469,6 +468,8 @@ DecPlan plan_decode(const Geometry &g) {
     p.lds2_bytes = 8 * (size_t)NB + 8 * 16 + 8 * 2 * MAXBANDS + 4 * 2 * MAXBANDS + 4 * (size_t)((p.bpp + 1) & ~1u)
                  + 4 * (size_t)p.in_cap_dw + 16 * (size_t)NB * dpr + align8(2 * (size_t)p.bpp * g.bands) + 2048;
     p.fast = simple && p.lds2_bytes <= 64 * 1024;
+    // the flags below say that a kernel APPLIES to the raster; the shapes they take (value size, band count, mode) do not overlap, and
+    // which one a launch uses -- with the pointers it is given -- is pick_dec_kernel's to say (k_dec_launch.hip)
     // 8-bit lane-per-block kernel
     bool rgb = false;
     p.px = p.fast && g.mode != CM_BEST && px_eligible(g, &rgb);
@@ -483,268 +484,35 @@ DecPlan plan_decode(const Geometry &g) {
     if (g.mode == CM_BEST && g.ulen_sz == 4 && NB == 64 && px_eligible(g, &rgb)) { p.px_best = true; p.px_rgb = rgb; }
     p.px16 = false; p.px16_bg = p.px16_ng = 0;
     bool rgb16 = false;
-    if (!p.px && p.fast && px16_eligible(g, &rgb16, &p.px16_bg, &p.px16_ng) && NB * p.px16_ng <= 64) {
+    if (p.fast && px16_eligible(g, &rgb16, &p.px16_bg, &p.px16_ng) && NB * p.px16_ng <= 64) {
         p.px16 = true; p.px_rgb = rgb16;
         p.px_cap_dw = (p.px_cap_dw + 4 + 3) & ~3u;             // staged from a 16-byte aligned word, in 16-byte pieces
-        p.lds_px = 4096 + 4 * 4 * ((size_t)p.px_cap_dw + 16);
+        p.lds_px = px16_lds_bytes(p.px_cap_dw);
     }
     // 32/64-bit, one band: a wave per 64-block segment; staging for the longest valid segment + WIDE_PAD_DW zero words, behind the 2 KB table
-    p.pxw = !p.px && !p.px16 && p.fast && pxw_eligible(g) && NB == 64;
+    p.pxw = p.fast && pxw_eligible(g) && NB == 64;
     p.lds_pxw = 0;
     if (p.pxw) {
         p.px_cap_dw = (uint32_t)(((size_t)NB * max_unit_bits(g.tsz, g.mode) + 31) / 32 + 2);
-        p.lds_pxw = 2048 + 4 * 4 * ((size_t)p.px_cap_dw + WIDE_PAD_DW);
+        p.lds_pxw = pxw_lds_bytes(p.px_cap_dw, true);
     }
     // ... and the common-factor streams of such rasters (the index has a dword per block: ulen_sz == 4); no table, no barrier
     p.pxw_best = g.ulen_sz == 4 && NB == 64 && pxw_eligible(g, true);
     if (p.pxw_best) {
         p.px_cap_dw = (uint32_t)(((size_t)NB * max_unit_bits(g.tsz, g.mode) + 31) / 32 + 2);
-        p.lds_pxw = 4 * 4 * ((size_t)p.px_cap_dw + WIDE_PAD_DW);
+        p.lds_pxw = pxw_lds_bytes(p.px_cap_dw, false);
     }
     // every other raster: a wave per segment of 64 / bands blocks, a lane per unit (k_dec_pxu.hip); core bands must themselves be core
     bool core_ok = true;
     for (uint32_t c = 0; c < g.bands; c++) core_ok = core_ok && g.cband[c] < g.bands && g.cband[g.cband[c]] == g.cband[c];
     const bool pxu_shape = lane_per_unit_shape(g.tsz, g.mode, g.bands) && NB == 64 / g.bands && core_ok && g.w >= 4 && g.h >= 4 && !tuning().no_px;
-    p.pxu = pxu_shape && g.mode != CM_BEST && g.ulen_sz != 0 && !p.px && !p.px16 && !p.pxw;
+    p.pxu = pxu_shape && g.mode != CM_BEST && g.ulen_sz != 0;
     p.pxu_best = pxu_shape && g.mode == CM_BEST && g.ulen_sz == ULEN_UNIT;
     if (p.pxu || p.pxu_best) p.px_cap_dw = (uint32_t)(((size_t)NB * g.bands * max_unit_bits(g.tsz, g.mode) + 31) / 32 + 2);
     return p;
 }
 
-// plain common-factor streams of several bands that walk by the chain (k_dec_walk_chain.hip, walk_chainN_kernel<UB, true>): 8- and 16-bit
-// rasters of the lane-per-unit decoder, and 8-bit RGBA (grey and RGB go by exits)
-static bool best_chain_applies(const Geometry &g, const DecPlan &plan) {
-    return g.mode == CM_BEST && g.tsz <= 2 && g.bands >= 2 && (plan.pxu_best || (plan.px_best && g.tsz == 1 && g.bands == 4));
-}
 size_t walk_table_cap() { return tuning().walk_tab_kb ? tuning().walk_tab_kb << 10 : (size_t)1 << 30; }
-bool walk_table_applies(const Geometry &g, const DecPlan &plan) {
-    // 8- and 16-bit rasters the lane-per-block decoders take; 32/64-bit rasters the unit-parallel decoder takes (a band of sixteen rungs)
-    // ... and single-band common-factor streams of any width (the exits of k_dec_walk.hip)
-    // ... common-factor streams of several bands of 8- and 16-bit data: the chain with the signal units parsed by the walking lane
-    if (g.mode == CM_BEST) return (g.bands == 1 || (g.bands == 3 && g.tsz == 1) || best_chain_applies(g, plan)) && !tuning().slow_walk && !tuning().slow_index;
-    // (8- and 16-bit rasters of the lane-per-unit decoder too: the 16-bit chain's kernels take any band count and segment size)
-    return (((plan.px || plan.pxu) && g.tsz == 1) || ((plan.px16 || plan.pxu) && g.tsz == 2) || (g.tsz >= 4 && plan.fast)) && !tuning().slow_walk && !tuning().slow_index;
-}
-
-// A restart table is untrusted input that the decoder takes positions, rungs and values from: its chunks are checked (ix_check_chunk,
-// qb3_kernels.h) -- by this kernel in front of the decoder, or by workgroups of the decoder's own launch (dec_px_kernel, DecArgs::chk_wgs).
-// A mismatch raises status bit 5; the host then decodes the call again without the table.  A workgroup per chunk.
-__global__ void __launch_bounds__(256) ix_check_kernel(const DecArgs a0) {
-    const DecArgs a = dec_for_tile(a0, blockIdx.y);
-    __shared__ uint32_t part[4];
-    ix_check_chunk(a, blockIdx.x, part);
-}
-
-static int launch_decode_all(const DecArgs &a, const DecPlan &plan, bool rebuild, hipStream_t st, void *walk_tab, size_t walk_tab_bytes, uint64_t max_bits) {
-    const bool best = a.g.mode == CM_BEST;
-    const bool use_px = plan.px && !best && a.g.tsz == 1;
-    const bool need_check = rebuild && a.ix && a.ix_K && (a.ix_ver >= 3 || a.ix_check_heads);
-    const bool use_px16 = plan.px16 && !best && a.g.tsz == 2 && ((uintptr_t)a.img & 1) == 0;
-    // 32/64-bit FTL/BASE streams that bring a restart table with an entry per index segment: the lengths-only walk too
-    const bool wide_walk = rebuild && a.ix && !best && a.g.tsz >= 4 && plan.fast && a.ix_blocks == a.g.seg_blocks && a.g.ulen_sz == 2;
-    const bool unit_parallel = !use_px && !use_px16 && plan.fast && !best && a.g.tsz >= 4;
-    // ... of them, one band: the lane-per-block decoder (a wave per segment) instead of the unit-parallel workgroup
-    const bool use_pxw = unit_parallel && plan.pxw && ((uintptr_t)a.img & (a.g.tsz - 1)) == 0 && !(a.ts_img & (a.g.tsz - 1));
-    // every raster no lane-per-block kernel takes: a lane per unit (value-aligned pointers)
-    const bool val_aligned = ((uintptr_t)a.img & (a.g.tsz - 1)) == 0 && !(a.ts_img & (a.g.tsz - 1));
-    const bool use_pxu = !use_px && !use_px16 && !use_pxw && plan.pxu && plan.fast && !best && val_aligned;
-    auto dec_units = [&](const DecArgs &t) {
-        if (use_px) launch_dec_px(t, plan, st); else if (use_px16) launch_dec_px16(t, plan, st); else if (use_pxw) launch_dec_pxw(t, plan, st);
-        else if (use_pxu) launch_dec_pxu(t, plan, st); else launch_dec_generic(t, plan, st);
-    };
-    const bool best_pxw = best && plan.pxw_best && ((uintptr_t)a.img & (a.g.tsz - 1)) == 0 && !(a.ts_img & (a.g.tsz - 1));
-    const bool best_pxu = best && plan.pxu_best && val_aligned;
-    const bool best_px = (best && plan.px_best && a.g.tsz == 1) || best_pxw || best_pxu;       // a lane-per-block (or per-unit) common-factor decoder applies
-    auto dec_best_lpb = [&](const DecArgs &t) { if (best_pxw) launch_dec_pxw_best(t, plan, st); else if (best_pxu) launch_dec_pxu_best(t, plan, st); else launch_dec_px_best(t, plan, st); };
-    // the table's check: the wave-per-segment decoders that work from the entries alone make it with the first workgroups of their own
-    // launch (DecArgs::chk_wgs: one launch, not two); everything else has ix_check_kernel in front
-    const bool from_entries = rebuild && a.ix && a.ix_bl && a.ix_blocks == a.g.seg_blocks && !tuning().slow_index && !tuning().no_bl;
-    const bool fold_check = need_check && from_entries && (best_px || (!best && (use_px || (use_px16 && ix_block_lens_ok(a.g)) || use_pxw || use_pxu)));
-    if (need_check && !fold_check)
-        hipLaunchKernelGGL(ix_check_kernel, dim3((a.ix_K + a.ix_per_chunk - 1) / a.ix_per_chunk, a.ntiles), dim3(256), 0, st, a);
-    if (rebuild && best_px && a.ix && a.ix_bl && a.ix_blocks == a.g.seg_blocks && !tuning().slow_index && !tuning().no_bl) {
-        // the container's table has a field per block (bits, entering rungs): the lane-per-block decoder works from the entries alone
-        DecArgs t = a;
-        t.bl_mode = 1;
-        if (fold_check) t.chk_wgs = (a.ix_K + a.ix_per_chunk - 1) / a.ix_per_chunk;
-        ProfScope ps("dec_units", st);
-        dec_best_lpb(t);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    if (rebuild && (use_px || (use_px16 && ix_block_lens_ok(a.g)) || unit_parallel || use_pxu) && a.ix && a.ix_bl && a.ix_blocks == a.g.seg_blocks && !tuning().slow_index && !tuning().no_bl) {
-        // the container's table carries block (16-bit data: band pair) lengths: the lane-per-block decoder works from the entries alone
-        DecArgs t = a;
-        t.bl_mode = 1;
-        if (fold_check) t.chk_wgs = (a.ix_K + a.ix_per_chunk - 1) / a.ix_per_chunk;
-        ProfScope ps("dec_units", st);
-        dec_units(t);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    // plain 32/64-bit FTL/BASE streams: unit lengths through the table of a band of rungs, when the caller brought memory for it
-    const bool wide_plain = rebuild && !a.ix && unit_parallel && walk_tab && walk_tab_bytes >= walk_table_min_bytes(a.ntiles, a.g.tsz) && !tuning().slow_walk;
-    const bool pxu16_plain = rebuild && !a.ix && use_pxu && a.g.tsz <= 2 && walk_tab && walk_tab_bytes >= walk_table_min_bytes(a.ntiles, a.g.tsz) && !tuning().slow_walk;
-    if (rebuild && (use_px || use_px16 || wide_walk || wide_plain || pxu16_plain) && !tuning().slow_index) {
-        // index-less stream through the lane-per-block kernels: walk the lengths, then let the parallel decoder itself
-        // produce the values entering the segments (totals pass + scan)
-        // plain 8-bit stream: through the table of unit lengths by position when the caller brought memory for it
-        const bool has_ix = a.ix != nullptr;
-        bool have_prev = false;             // the index's entering values are there already
-        if ((use_px || use_px16 || wide_plain || pxu16_plain) && !has_ix && walk_tab && walk_tab_bytes >= walk_table_min_bytes(a.ntiles, a.g.tsz) && !tuning().slow_walk) launch_dec_walk_table(a, st, walk_tab, walk_tab_bytes, max_bits);
-        else if (has_ix) { ProfScope ps("dec_index_serial", st); launch_dec_walk(a, st); }
-        else { ProfScope ps("dec_index_serial", st); launch_dec_index_serial(a, st); have_prev = true; }       // no table memory: one lane parses the stream (values included)
-        if (!have_prev && !(a.ix && a.ix_blocks == a.g.seg_blocks) && !wide_walk) {         // (an entry per segment: the walk copied the entering values)
-          {
-            ProfScope ps("dec_index_prev", st);
-            DecArgs t = a;
-            t.totals_only = 1;
-            dec_units(t);
-          }
-          ProfScope ps("dec_index_scan", st);
-          launch_prev_scan(a, st);
-        }
-    } else if (rebuild && !a.from_ix) {
-        // plain single-band common-factor streams: segment entries by the walk through exits, entering values by a scan
-        // of the segments' sums; anything else (and that walk when it has no memory): one lane parses the stream
-        const bool best_plain = best && !a.ix && (a.g.bands == 1 || ((a.g.bands == 3 || a.g.bands == 2) && a.g.tsz == 1)) && walk_tab && walk_tab_bytes >= walk_table_min_bytes(a.ntiles, a.g.tsz) &&
-                                !tuning().slow_walk && !tuning().slow_index && launch_dec_walk_best(a, st, walk_tab, walk_tab_bytes, max_bits);
-        // ... of several bands (8- and 16-bit data): the chain, the walking lane parsing the units with the signal code; values as below
-        const bool best_chain = best && !best_plain && !a.ix && best_chain_applies(a.g, plan) && walk_tab && walk_tab_bytes >= walk_table_min_bytes(a.ntiles, a.g.tsz) &&
-                                walk_chain_lds_ok() && !tuning().slow_walk && !tuning().slow_index;
-        if (best_plain) { ProfScope ps("dec_index_scan", st); launch_prev_scan(a, st); }
-        else if (best_chain) {
-            {   // the factors in force start from zero (the lane writes them from the first unit that brings one on); the block table is added up
-                const size_t cfb = (size_t)a.g.nseg * a.g.bands * a.g.tsz, ulb = a.g.ulen_sz == 4 ? (size_t)a.g.nblocks * 4 : 0;
-                if (a.ntiles > 1) { (void)hipMemset2DAsync(a.idx.cf, a.ts_idx, 0, cfb, a.ntiles, st); if (ulb) (void)hipMemset2DAsync(a.idx.ulen, a.ts_idx, 0, ulb, a.ntiles, st); }
-                else { (void)hipMemsetAsync(a.idx.cf, 0, cfb, st); if (ulb) (void)hipMemsetAsync(a.idx.ulen, 0, ulb, st); }
-            }
-            if (a.g.tsz == 2) walk_chain_16bit(a, st, walk_tab, walk_tab_bytes, max_bits); else walk_chain_8bit_any(a, st, walk_tab, walk_tab_bytes, max_bits);
-            { ProfScope ps("dec_index_prev", st); DecArgs t = a; t.totals_only = 1; if (best_pxu) launch_dec_pxu_best(t, plan, st); else launch_dec_generic(t, plan, st); }
-            ProfScope ps("dec_index_scan", st);
-            launch_prev_scan(a, st);
-        }
-        else if (best && !a.ix && dec_index_walk_best_ok(a) && !tuning().slow_index) {
-            // common-factor streams the exits do not take (several bands; no table memory): one wave walks lengths (units with
-            // the signal code parsed outright), the generic decoder adds up every segment's values, a scan makes entering values
-            // of the sums
-            { ProfScope ps("dec_index_serial", st); launch_dec_index_walk_best(a, st); }
-            { ProfScope ps("dec_index_prev", st); DecArgs t = a; t.totals_only = 1; if (best_pxu) launch_dec_pxu_best(t, plan, st); else launch_dec_generic(t, plan, st); }
-            ProfScope ps("dec_index_scan", st);
-            launch_prev_scan(a, st);
-        }
-        else { ProfScope ps("dec_index_serial", st); launch_dec_index_serial(a, st); }
-    }
-    if (best_px && !a.from_ix) { ProfScope ps("dec_units", st); dec_best_lpb(a); }
-    else if (use_px) { ProfScope ps("dec_units", st); launch_dec_px(a, plan, st); }
-    else if (use_px16) { ProfScope ps("dec_units", st); launch_dec_px16(a, plan, st); }
-    else if (use_pxw) { ProfScope ps("dec_units", st); launch_dec_pxw(a, plan, st); }
-    else if (use_pxu) { ProfScope ps("dec_units", st); launch_dec_pxu(a, plan, st); }
-    else { ProfScope ps(plan.fast && !best ? "dec_units" : "dec_segments", st); launch_dec_generic(a, plan, st); }
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int launch_decode(const Geometry &g, const DecPlan &plan_in, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
-                  void *img, const void *index, void *ws, uint32_t **status_out, void *stream, const TileBatch &tb,
-                  const uint64_t *tile_bits, const IxTable &ix, void *walk_tab, size_t walk_tab_bytes, bool full_staging, uint32_t wide_band, const DecStrip *strip) {
-    hipStream_t st = (hipStream_t)stream;
-    DecArgs a;
-    // 16-bit lane-per-block decoder: a wave stages its segment in LDS, and four worst-case segments (278 bits a unit) keep
-    // the CU at 4 workgroups.  Size the staging for a third above THIS stream's average segment instead; a segment that
-    // does not fit raises status bit 4 and the caller runs the call again with full_staging.
-    DecPlan plan = plan_in;
-    if (plan.px16 && !full_staging && g.nseg) {
-        const uint64_t bits = tb.n ? tb.max_bits : in_bits;
-        uint64_t cap = bits / 32 / g.nseg;
-        cap = (cap + cap / 3 + 64 + 3) & ~(uint64_t)3;
-        if (bits && cap < plan.px_cap_dw) { plan.px_cap_dw = (uint32_t)cap; plan.lds_px = 4096 + 4 * 4 * ((size_t)cap + 16); }
-    }
-    if ((plan.pxw || plan.pxw_best) && !full_staging && g.nseg) {          // the same for 32/64-bit data (worst case: 4.3 / 8.4 KB a wave)
-        const uint64_t bits = tb.n ? tb.max_bits : in_bits;
-        uint64_t cap = bits / 32 / g.nseg;
-        cap = (cap + cap / 2 + 64 + 3) & ~(uint64_t)3;
-        if (bits && cap < plan.px_cap_dw) { plan.px_cap_dw = (uint32_t)cap; plan.lds_pxw = (plan.pxw ? 2048 : 0) + 4 * 4 * ((size_t)cap + WIDE_PAD_DW); }
-    }
-    if ((plan.pxu || plan.pxu_best) && !full_staging && g.nseg) {        // ... and for the lane-per-unit kernels
-        const uint64_t bits = tb.n ? tb.max_bits : in_bits;
-        uint64_t cap = bits / 32 / g.nseg;
-        cap = (cap + cap / 2 + 64 + 3) & ~(uint64_t)3;
-        if (bits && cap < plan.px_cap_dw) plan.px_cap_dw = (uint32_t)cap;
-    }
-    a.in_cap_full = plan_in.px_cap_dw;
-    // the container's coarse restart table is usable when it matches this geometry and this library's segments
-    a.ix = nullptr; a.ix_K = a.ix_blocks = a.ix_E = a.ix_per_chunk = a.ix_pad = 0; a.ix_bl = 0; a.ix_ver = 0; a.ix_check_heads = 0; a.chk_wgs = 0;
-    if (ix.base && ix.blocks && ix.per_chunk && ix.blocks % g.seg_blocks == 0 && ix.entry_bytes == ix_entry_bytes(g, ix.block_lens) &&
-        (!ix.block_lens || (ix_block_lens_ok(g) && ix.blocks == g.seg_blocks)) &&
-        ix.K == (g.nblocks + ix.blocks - 1) / ix.blocks) {
-        a.ix = ix.base; a.ix_K = ix.K; a.ix_blocks = ix.blocks; a.ix_E = ix.entry_bytes; a.ix_per_chunk = ix.per_chunk;
-        a.ix_pad = ix.pads ? IX_PAD : 0;
-        a.ix_bl = ix.block_lens;
-        a.ix_ver = ix.version; a.ix_check_heads = ix.check_heads ? 1u : 0u;
-    }
-    // lane-per-segment decoder: LDS for the stream words of a workgroup's segments, half as much again as the average,
-    // when that is at most 24 KB (more would cost more in resident workgroups than the staging saves; a longer span is
-    // read from global memory).  With a restart table in the container and no index, the lanes decode straight from the
-    // table's entries (from_ix: no index is rebuilt at all; their pieces are long, so usually not staged).
-    a.seg_cap_dw = 0;
-    const bool lane_per_segment = !(plan.fast && g.mode != CM_BEST);
-    a.from_ix = (lane_per_segment && index == nullptr && a.ix && !tuning().slow_index) ? 1u : 0u;
-    if (g.nseg && lane_per_segment) {
-        const uint64_t bits = tb.n ? tb.max_bits : in_bits;
-        uint64_t cap = bits / 32 * plan.threads / (a.from_ix ? a.ix_K : g.nseg);
-        cap = (cap + cap / 2 + 64 + 3) & ~(uint64_t)3;
-        if (bits && cap <= 24 * 1024 / 4) a.seg_cap_dw = (uint32_t)cap;
-    }
-    a.g = g; a.in32 = in32; a.in_bit0 = in_bit0; a.in_bits = in_bits; a.img = img;
-    a.ntiles = tb.n ? tb.n : 1; a.ts_in = tb.src_pitch; a.ts_img = tb.dst_pitch; a.tile_bits = tile_bits;
-    uint8_t *w = (uint8_t *)ws;
-    const bool rebuild = index == nullptr;
-    // workspace: [status words, 64 bytes per 16 tiles][rebuilt indices, one per tile]
-    const size_t status_bytes = ((4 * (size_t)a.ntiles + 63) / 64) * 64;
-    a.status = (uint32_t *)w;
-    a.idx = index_view(g, rebuild ? (void *)(w + status_bytes) : const_cast<void *>(index));
-    a.ts_idx = rebuild ? align8(index_bytes(g)) : tb.idx_pitch;
-    if (!strip || strip->first) HIPCHK(hipMemsetAsync(a.status, 0, status_bytes, st));
-    a.seg0 = strip ? strip->seg0 : 0;
-    a.seg_end = strip ? std::min<uint64_t>(g.nseg, strip->seg0 + strip->nseg) : g.nseg;
-    a.lane_dw = dec_lane_dwords(g);
-    a.dpr = g.bands * g.tsz;
-    a.bpp = plan.bpp; a.passes = plan.passes; a.in_cap_dw = (plan.px || plan.px16 || plan.px_best || plan.pxw || plan.pxw_best || plan.pxu || plan.pxu_best) ? plan.px_cap_dw : plan.in_cap_dw;
-    a.px_ng = plan.px16 ? plan.px16_ng : 1; a.px_magic_ng = magic_div(a.px_ng);
-    a.totals_only = 0;
-    a.bl_mode = 0;
-    a.wide_band = tuning().wide_band ? (uint32_t)tuning().wide_band : wide_band;
-    a.px_aligned = !(g.w & 3) && !((g.stride * g.tsz) & 3) && !((uintptr_t)img & 3) && !(tb.dst_pitch & 3);
-    a.magic_bpp = magic_div(plan.bpp); a.magic_dpr = magic_div(a.dpr); a.magic_bands = magic_div(g.bands);
-    *status_out = a.status;
-    if (g.tsz != 1 && g.tsz != 2 && g.tsz != 4 && g.tsz != 8) { set_error("decode: bad value size", 0); return -1; }
-    if (strip) {        // one launch of the lane-per-block decoder over the strip's segments, from the table's entries
-        if (rebuild && strip->first && a.ix && a.ix_K && (a.ix_ver >= 3 || a.ix_check_heads))
-            hipLaunchKernelGGL(ix_check_kernel, dim3((a.ix_K + a.ix_per_chunk - 1) / a.ix_per_chunk, a.ntiles), dim3(256), 0, st, a);
-        if (!rebuild || !a.ix || !decode_strips_ok(g, plan_in, ix)) { set_error("decode: strips need the container's table", 0); return -1; }
-        a.bl_mode = 1;
-        ProfScope ps("dec_units", st);
-        const bool best = g.mode == CM_BEST;
-        if (best && plan.pxw_best) launch_dec_pxw_best(a, plan, st);
-        else if (best && plan.pxu_best) launch_dec_pxu_best(a, plan, st);
-        else if (best) launch_dec_px_best(a, plan, st);
-        else if (plan.px) launch_dec_px(a, plan, st);
-        else if (plan.px16) launch_dec_px16(a, plan, st);
-        else if (plan.pxu) launch_dec_pxu(a, plan, st);
-        else launch_dec_pxw(a, plan, st);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    return launch_decode_all(a, plan, rebuild, st, walk_tab, walk_tab_bytes, tb.n ? tb.max_bits : in_bits);
-}
-
-bool decode_strips_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix) {
-    if (!ix.base || !ix.block_lens || !ix.blocks || ix.blocks != g.seg_blocks || !ix.per_chunk || tuning().slow_index || tuning().no_bl) return false;
-    if (ix.entry_bytes != ix_entry_bytes(g, true) || !ix_block_lens_ok(g) || ix.K != (g.nblocks + ix.blocks - 1) / ix.blocks) return false;
-    if (g.mode == CM_BEST) return (plan.px_best && g.tsz == 1) || plan.pxw_best || plan.pxu_best;
-    return (plan.px && g.tsz == 1) || (plan.px16 && g.tsz == 2) || plan.pxw || (plan.pxu && plan.fast);
-}
 
 }  // namespace qb3dev
 

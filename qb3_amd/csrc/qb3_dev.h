@@ -199,6 +199,8 @@ int launch_encode_strip(const Geometry &g, const EncPlan &plan, const void *img,
 int launch_encode_tail(const Geometry &g, const EncPlan &plan, const void *img, uint32_t *out32, uint32_t out_bit0,
                        const BandState &st_in, void *ws, void *index, void *stream, const uint8_t *hdr, uint32_t hdr_len, const IxTable &ix);
 
+// What decodes a raster.  The bool flags say that a kernel APPLIES to the geometry (plan_decode); which one a launch uses, given the
+// pointers it gets, is decided in one place: pick_dec_kernel (k_dec_launch.hip), and what runs in front of it next to that (DecFront).
 struct DecPlan {
     uint32_t threads;       // lanes per workgroup, one index segment per lane
     uint32_t nwg;
@@ -221,6 +223,15 @@ struct DecPlan {
     bool pxu, pxu_best;     // the lane-per-unit decoders apply (k_dec_pxu.hip: lane_per_unit_shape): FTL / BASE, common factor
 };
 DecPlan plan_decode(const Geometry &g);
+// LDS of the decoders that stage a wave's segment, from px_cap_dw: 16-bit data (table, four waves' staging); 32/64-bit data (FTL / BASE: a 2 KB table in front)
+inline size_t px16_lds_bytes(uint32_t cap_dw) { return 4096 + 4 * 4 * ((size_t)cap_dw + 16); }
+inline size_t pxw_lds_bytes(uint32_t cap_dw, bool table) { return (table ? 2048 : 0) + 4 * 4 * ((size_t)cap_dw + WIDE_PAD_DW); }
+
+// The kernel that decodes the units of a launch: the one of the plan's that applies and whose alignment needs the image pointer and the tile pitch (bytes)
+// meet, else the generic one (the unit-parallel workgroup for FTL / BASE streams it takes, else a lane per segment).
+enum class DecKernel { generic, px, px16, pxw, pxu, px_best, pxw_best, pxu_best };
+DecKernel pick_dec_kernel(const Geometry &g, const DecPlan &plan, const void *img, uint64_t pitch);
+inline DecKernel aligned_dec_kernel(const Geometry &g, const DecPlan &plan) { return pick_dec_kernel(g, plan, nullptr, 0); }   // ... with aligned memory
 
 struct DecStrip { uint64_t seg0, nseg; bool first; };     // first: zero the status words, check the table; later strips skip both
 // Decode a block stream.  in32/in_bit0 locate the first stream bit like out32/out_bit0 above; in_bits is
@@ -235,7 +246,7 @@ int launch_decode(const Geometry &g, const DecPlan &plan, const uint32_t *in32, 
                   bool full_staging = false,    // 16-bit data: worst-case LDS staging (after a call that ended with status bit 4)
                   uint32_t wide_band = 16,      // plain 32/64-bit streams: rungs the walk's table covers (16; 14: byte entries, 8: half rows -- QB3_WIDE_BAND, test hooks; the first
                                                 // unit of a block row, entered from the far end of the row before, sits many rungs above its neighbours)
-                  const DecStrip *strip = nullptr);     // a strip of a pipelined host call (decode_strips_ok): only these segments, from the container's table
+                  const DecStrip *strip = nullptr);     // a strip of a pipelined host call (decode_strips_ok): only these segments, from the container's table; value-aligned img and pitch, else refused
 
 // can a container's table (with block fields, an entry per index segment) be decoded strip by strip: one launch of a
 // lane-per-block decoder per range of segments, nothing else

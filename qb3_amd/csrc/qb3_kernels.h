@@ -618,6 +618,8 @@ struct Tuning { bool no_px; bool slow_index; bool slow_walk; bool no_bl; size_t 
 const Tuning &tuning();
 
 uint32_t magic_div(uint32_t d);
+inline size_t align8(size_t v) { return (v + 7) & ~(size_t)7; }
+uint32_t dec_lane_dwords(const Geometry &g);       // LDS dwords per lane of the lane-per-segment decoder (k_host.hip)
 uint32_t max_unit_bits(uint32_t tsz, uint32_t mode = CM_FTL);
 
 // launchers, one per translation unit; they enqueue on `st` and return nothing (errors surface through hipGetLastError)
