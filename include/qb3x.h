@@ -68,6 +68,10 @@ size_t qb3x_decode_device(decsp p, const void *d_src, void *d_dst, const void *d
  *   1  8-bit rasters of 1, 3 or 4 bands, FTL / BASE, level-2 table in the container, d_index NULL: one kernel decodes the index
  *      segments that hold a block of the window -- and no others -- straight into d_dst; of the table only the chunks the window's
  *      entries are read from are checked and read.  Time and memory follow the window, not the raster.
+ *      On a handle with qb3x_set_decoder_window_kernels(p, QB3X_WINK_U16) path 1 also takes 16-bit rasters of 1, 2, 3, 4, 6 or 8
+ *      bands (FTL / BASE, level-2 table of version 3, d_dst on an even address; else they go as below): the same, with the
+ *      raster's blocks per segment (64, 32 for eight bands, 21 for six) -- time follows the window, and a handle that only ever
+ *      takes path 1 allocates no scratch raster.  Path, segment count and status are reported with path 1's meaning.
  *   2  every other raster with a level-2 table (16-bit, 32/64-bit, other band counts, the common-factor modes): the segments of the
  *      window's block ROWS are decoded into a scratch raster the handle owns, then cropped.  Time follows the window's rows; the
  *      scratch is raster sized (qb3_decoded_size bytes of device memory).
@@ -96,6 +100,13 @@ size_t qb3x_window_segments(const decsp p, size_t x0, size_t y0, size_t w, size_
  * window; 2: those of its block rows; 3: all of the raster's, 0 where there is no block grid). */
 int    qb3x_last_window_path(const decsp p);
 size_t qb3x_last_window_segments(const decsp p);
+/* Rasters beyond path 1's own that take a window kernel, per decoder handle; default 0: every window call goes as described above.
+ * Honoured by qb3x_decode_window_device, qb3x_decode_windows_device, qb3x_read_window and qb3x_read_windows; the ranged calls do
+ * not look at it.  Unknown bits are ignored; a NULL handle: no-op.  The bytes are the same with and without a bit: the bit only
+ * chooses the way.  Harmless on a handle whose raster the kernels do not take (8-bit data, other band counts, the common-factor
+ * modes, STORED containers, narrow images, a level-1 table). */
+#define QB3X_WINK_U16 1u   /* 16-bit rasters of 1, 2, 3, 4, 6, 8 bands, FTL / BASE, level-2 table: window kernel (path 1) instead of strips (path 2) */
+void qb3x_set_decoder_window_kernels(decsp p, unsigned mask);
 
 /* A batch of windows: n rectangles of ONE raster in one call -- what a tile server, a viewer or a cropping loader asks of a raster
  * it keeps in device memory.  wins is a HOST array; dst is a device pointer for qb3x_decode_windows_device and a host pointer for
@@ -313,7 +324,7 @@ size_t qb3_decode(decsp p, void *destination);                                  
  * events on the launch stream; totals are resolved at the library's own synchronisation points.
  * Kernel names: enc_units, enc_scan, enc_concat, enc_seams, enc_best_units, enc_best_scan, enc_best_recode,
  * dec_index_table, dec_index_serial, dec_index_prev, dec_index_scan, dec_units, dec_segments, dec_window (the window kernel of
- * qb3x_decode_window_device, path 1), dec_window_ranged (the same from fetched pieces: the ranged calls), reindex_fill, reindex_finish (qb3x_reindex_device: the table's entries; everything else of the
+ * qb3x_decode_window_device, path 1), dec_window16 (the 16-bit window kernels: path 1 under QB3X_WINK_U16), dec_window_ranged (the same from fetched pieces: the ranged calls), reindex_fill, reindex_finish (qb3x_reindex_device: the table's entries; everything else of the
  * new container).
  * level: 0 off, 1 every kernel, 2 all but the microsecond kernels (enc_scan, enc_seams, enc_best_scan), whose two
  * events cost more than they take. */

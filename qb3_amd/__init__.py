@@ -31,6 +31,7 @@ QB3_U8, QB3_I8, QB3_U16, QB3_I16, QB3_U32, QB3_I32, QB3_U64, QB3_I64 = range(8)
 QB3M_BASE_Z, QB3M_CF, QB3M_RLE, QB3M_CF_RLE, QB3M_BASE_H, QB3M_CF_H, QB3M_RLE_H, QB3M_CF_RLE_H, QB3M_FTL = range(9)
 QB3M_DEFAULT, QB3M_BASE, QB3M_BEST, QB3M_STORED, QB3M_INVALID = 8, 4, 7, 255, -1
 QB3X_REF_CBAND0 = 1
+QB3X_WINK_U16 = 1           # qb3x_set_decoder_window_kernels: the 16-bit window kernels
 TYPESIZE = (1, 1, 2, 2, 4, 4, 8, 8)
 
 _vp, _sz, _u64 = C.c_void_p, C.c_size_t, C.c_uint64
@@ -114,6 +115,7 @@ _PROTOS = {
     "qb3x_header_size_bound": (_sz, [_vp, _sz]),
     "qb3x_decoder_table_entries": (_sz, [_vp]),
     "qb3x_set_decoder_compat": (None, [_vp, C.c_uint]),
+    "qb3x_set_decoder_window_kernels": (None, [_vp, C.c_uint]),
     "qb3x_reindex_size": (_sz, [_vp, C.c_int]),
     "qb3x_reindex_device": (_sz, [_vp, _vp, _vp, _sz, C.c_int, _vp]),
     "qb3x_reindex": (_sz, [_vp, _sz, _vp, _sz, C.c_int]),

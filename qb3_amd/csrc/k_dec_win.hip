@@ -28,13 +28,6 @@
 
 namespace qb3dev {
 
-struct WinArgs {
-    DecArgs d;                      // stream, table, status word, staging capacity: as dec_px_kernel takes them
-    WinDesc w;                      // the window: destination, rectangle in pixels and blocks, waves (qb3_win.h)
-    uint32_t chk0, chk_n;           // table chunks the launch's first chk_n workgroups check, from chunk chk0
-    uint32_t tail_chunk;            // the workgroup behind them checks the table's last chunk too (it is not one of those)
-};
-
 // ... for the strip of block rows of a window call (path 2), whose launch has checked the whole table: one lane
 __global__ void ix_tail_kernel(const DecArgs a) { if (threadIdx.x == 0) ix_tail_check(a); }
 
@@ -84,6 +77,20 @@ void window_dec_args(DecArgs &a, const Geometry &g, const DecPlan &plan, const u
     a.ntiles = 1; a.seg0 = 0; a.seg_end = g.nseg;
 }
 
+uint32_t window_launch_args(WinArgs &wa, const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
+                            void *dst, const WinRect &r, uint32_t *status, const IxTable &ix) {
+    DecArgs &a = wa.d;
+    window_dec_args(a, g, plan, in32, in_bit0, in_bits, status, ix);
+    window_desc(g, r, dst, &wa.w);
+    // table chunks an entry is read from: the first segment's to the one of the entry behind the last segment
+    const uint64_t first = ((uint64_t)wa.w.by0 * g.nbx + wa.w.bx0) / g.seg_blocks, last = std::min<uint64_t>(((uint64_t)wa.w.by1 * g.nbx + wa.w.bx1) / g.seg_blocks + 1, ix.K - 1);
+    wa.chk0 = (uint32_t)(first / ix.per_chunk);
+    const bool checked = a.ix_ver >= 3 || a.ix_check_heads;
+    wa.chk_n = checked ? (uint32_t)(last / ix.per_chunk) - wa.chk0 + 1 : 0;
+    wa.tail_chunk = checked && (ix.K - 1) / ix.per_chunk > last / ix.per_chunk;
+    return wa.chk_n + 1 + (wa.w.nwaves + 3) / 4;
+}
+
 template <int B, bool RGB>
 static void launch_dec_win_b(const WinArgs &wa, dim3 grid, size_t lds, hipStream_t st) {
     const bool step = wa.d.g.mode != CM_FTL, z = wa.d.g.order == ZCURVE;
@@ -99,17 +106,8 @@ int launch_decode_window(const Geometry &g, const DecPlan &plan, const uint32_t 
     hipStream_t st = (hipStream_t)stream;
     if (!decode_window_ok(g, plan, ix) || !window_segments(g, r) || r.stride < (uint64_t)r.w * g.bands) { set_error("window decode: not for this raster", 0); return -1; }
     WinArgs wa = {};
-    DecArgs &a = wa.d;
-    window_dec_args(a, g, plan, in32, in_bit0, in_bits, status, ix);
-    window_desc(g, r, dst, &wa.w);
-    // table chunks an entry is read from: the first segment's to the one of the entry behind the last segment
-    const uint64_t first = ((uint64_t)wa.w.by0 * g.nbx + wa.w.bx0) / 64, last = std::min<uint64_t>(((uint64_t)wa.w.by1 * g.nbx + wa.w.bx1) / 64 + 1, ix.K - 1);
-    wa.chk0 = (uint32_t)(first / ix.per_chunk);
-    const bool checked = a.ix_ver >= 3 || a.ix_check_heads;
-    wa.chk_n = checked ? (uint32_t)(last / ix.per_chunk) - wa.chk0 + 1 : 0;
-    wa.tail_chunk = checked && (ix.K - 1) / ix.per_chunk > last / ix.per_chunk;
+    const dim3 grid(window_launch_args(wa, g, plan, in32, in_bit0, in_bits, dst, r, status, ix));
     HIPCHK(hipMemsetAsync(status, 0, 4, st));
-    const dim3 grid(wa.chk_n + 1 + (wa.w.nwaves + 3) / 4);
     {
         ProfScope ps("dec_window", st);
         if (g.bands == 1) launch_dec_win_b<1, false>(wa, grid, plan.lds_px, st);

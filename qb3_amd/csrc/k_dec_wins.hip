@@ -16,14 +16,6 @@
 
 namespace qb3dev {
 
-struct WinBatchArgs {
-    DecArgs d;                      // stream, table, staging capacity; d.status: the call-wide word
-    const WinDesc *wins;            // the launch's windows, wave0 counted from the launch's first window
-    uint32_t *wstatus;              // ... their status words
-    const uint32_t *chunks;         // table chunks to check, chk_n of them (the first launch of a call only)
-    uint32_t nwin, chk_n, tail;     // tail: a workgroup behind the chunk checks does the tail check
-};
-
 template <int B, bool RGB, uint64_t ORDER, bool STEP>
 __global__ void __launch_bounds__(256) dec_wins_kernel(const WinBatchArgs ba) {
     const DecArgs &a = ba.d;
@@ -74,7 +66,7 @@ size_t window_batch_plan(const Geometry &g, const IxTable &ix, const WinRect *re
         waves += d[i].nwaves;
         segs += window_segments(g, rects[i]);
         if (checked) {      // table chunks an entry is read from: the first segment's to the one of the entry behind the last segment
-            const uint64_t first = ((uint64_t)d[i].by0 * g.nbx + d[i].bx0) / 64, last = std::min<uint64_t>(((uint64_t)d[i].by1 * g.nbx + d[i].bx1) / 64 + 1, ix.K - 1);
+            const uint64_t first = ((uint64_t)d[i].by0 * g.nbx + d[i].bx0) / g.seg_blocks, last = std::min<uint64_t>(((uint64_t)d[i].by1 * g.nbx + d[i].bx1) / g.seg_blocks + 1, ix.K - 1);
             for (uint64_t c = first / ix.per_chunk; c <= last / ix.per_chunk; c++) chunks.push_back((uint32_t)c);
         }
     }
@@ -92,23 +84,15 @@ int launch_decode_windows(const Geometry &g, const DecPlan &plan, const uint32_t
                           uint32_t *d_status, void *stream, const IxTable &ix) {
     hipStream_t st = (hipStream_t)stream;
     if (!decode_window_ok(g, plan, ix) || !n) { set_error("window batch: not for this raster", 0); return -1; }
-    const WinDesc *h = (const WinDesc *)h_descs;
     WinBatchArgs ba = {};
     window_dec_args(ba.d, g, plan, in32, in_bit0, in_bits, d_status, ix);
-    for (size_t first = 0; first < n;) {                // one launch, unless the waves exceed WIN_LAUNCH_WAVES
-        size_t end = first + 1;
-        while (end < n && h[end].wave0 != 0) end++;
-        const uint64_t waves = (uint64_t)h[end - 1].wave0 + h[end - 1].nwaves;
-        ba.wins = (const WinDesc *)d_descs + first; ba.wstatus = d_status + 1 + first; ba.nwin = (uint32_t)(end - first);
-        ba.chunks = d_chunks; ba.chk_n = first ? 0 : (uint32_t)nchunks; ba.tail = first ? 0 : 1;
-        const dim3 grid((uint32_t)(ba.chk_n + ba.tail + (waves + 3) / 4));
+    window_batch_launches(ba, h_descs, d_descs, n, d_chunks, nchunks, d_status, [&](const WinBatchArgs &ba, dim3 grid) {
         ProfScope ps("dec_window", st);
         if (g.bands == 1) launch_dec_wins_b<1, false>(ba, grid, plan.lds_px, st);
         else if (g.bands == 3) { if (plan.px_rgb) launch_dec_wins_b<3, true>(ba, grid, plan.lds_px, st); else launch_dec_wins_b<3, false>(ba, grid, plan.lds_px, st); }
         else { if (plan.px_rgb) launch_dec_wins_b<4, true>(ba, grid, plan.lds_px, st); else launch_dec_wins_b<4, false>(ba, grid, plan.lds_px, st); }
-        HIPCHK(hipGetLastError());
-        first = end;
-    }
+    });
+    HIPCHK(hipGetLastError());
     return 0;
 }
 

@@ -282,6 +282,16 @@ size_t window_batch_plan(const Geometry &g, const IxTable &ix, const WinRect *re
 int launch_decode_windows(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
                           const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
                           uint32_t *d_status, void *stream, const IxTable &ix);
+// The 16-bit window kernels (k_dec_win16.hip): rasters of 1, 2, 3, 4, 6 or 8 bands, FTL / BASE, whose level-2 table (version 3) carries
+// the lane fields dec_px16_kernel decodes a segment from alone.  decode_window16_ok: does the raster and its table qualify (the host
+// also asks the handle's switch, qb3x_set_decoder_window_kernels, before it takes them).  The launchers are their 8-bit counterparts'
+// in everything but the kernels: arguments, descriptors (window_batch_plan), status words; dst must be halfword aligned.
+bool decode_window16_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix);
+int launch_decode_window16(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
+                           void *dst, const WinRect &r, uint32_t *status, void *stream, const IxTable &ix);
+int launch_decode_windows16(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
+                            const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
+                            uint32_t *d_status, void *stream, const IxTable &ix);
 // The same from PIECES of the container (k_dec_wins_ranged.hip; api_ranged.cpp fetches them): d_pieces: npieces >= 1 pieces sorted by
 // first segment, each a run of consecutive segments { seg0, nseg, ent0, word0, stream word of its first packed word (low, high),
 // nwords, 0 }; d_entries: the compact array of table entries (ix.entry_bytes each), nseg + 1 per piece from index ent0; d_words: the

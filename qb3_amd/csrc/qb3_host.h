@@ -119,6 +119,7 @@ struct decs {
     DevBuf d_win, d_wst, d_wout, d_wsrc;               // window calls: the raster a strip or a whole decode goes to before the crop; the window kernel's status word; a host call's window and container
     int win_path = 0;                                  // ... which way the last one went (qb3x_last_window_path) and how many segments it decoded
     size_t win_segs = 0;
+    unsigned win_kernels = 0;                          // qb3x_set_decoder_window_kernels: rasters beyond path 1's own that take a window kernel (QB3X_WINK_*)
     DevBuf d_wdesc;                                    // a batch of windows: descriptors and the list of table chunks to check, as uploaded
     PinBuf h_wdesc, h_wst;                             // ... their pinned host copy (one copy up), and the status words (one copy back)
     std::vector<uint8_t> wins_path;                    // ... per window outcome of the last batch call (0: not written, else its path)

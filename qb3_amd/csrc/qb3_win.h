@@ -26,14 +26,50 @@ inline void window_desc(const Geometry &g, const WinRect &r, void *dst, WinDesc 
     w->bx0 = std::min(r.x0 / 4, g.nbx - 1); w->bx1 = std::min((r.x0 + r.w - 1) / 4, g.nbx - 1);
     w->by0 = std::min(r.y0 / 4, g.nby - 1); w->by1 = std::min((r.y0 + r.h - 1) / 4, g.nby - 1);
     // the most segments the run of bx1 - bx0 + 1 blocks of a row touches: it starts anywhere in a segment, unless rows start where segments do
-    const uint32_t n = w->bx1 - w->bx0 + 1;
-    w->per_row = (g.nbx % 64 == 0) ? (w->bx0 % 64 + n - 1) / 64 + 1 : (n + 62) / 64 + 1;
+    // (NB blocks a segment: 64 for the 8-bit kernels, 64 / band groups for the 16-bit ones)
+    const uint32_t n = w->bx1 - w->bx0 + 1, NB = g.seg_blocks;
+    w->per_row = (g.nbx % NB == 0) ? (w->bx0 % NB + n - 1) / NB + 1 : (n + NB - 2) / NB + 1;
     w->nwaves = (w->by1 - w->by0 + 1) * w->per_row;
     w->wave0 = 0; w->pad_ = 0;
 }
 // what a window kernel takes from the raster, the stream and the table (status: the word ix_check_chunk and ix_tail_check raise bits in)
 void window_dec_args(DecArgs &a, const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
                      uint32_t *status, const IxTable &ix);
+
+// what the single kernels take (dec_win_kernel, dec_win16_kernel) ...
+struct WinArgs {
+    DecArgs d;                      // stream, table, status word, staging capacity: as dec_px_kernel takes them
+    WinDesc w;                      // the window: destination, rectangle in pixels and blocks, waves (qb3_win.h)
+    uint32_t chk0, chk_n;           // table chunks the launch's first chk_n workgroups check, from chunk chk0
+    uint32_t tail_chunk;            // the workgroup behind them checks the table's last chunk too (it is not one of those)
+};
+// ... and the batch kernels (dec_wins_kernel, dec_wins16_kernel)
+struct WinBatchArgs {
+    DecArgs d;                      // stream, table, staging capacity; d.status: the call-wide word
+    const WinDesc *wins;            // the launch's windows, wave0 counted from the launch's first window
+    uint32_t *wstatus;              // ... their status words
+    const uint32_t *chunks;         // table chunks to check, chk_n of them (the first launch of a call only)
+    uint32_t nwin, chk_n, tail;     // tail: a workgroup behind the chunk checks does the tail check
+};
+// fills wa for one window (status: zeroed by the caller's launch) and returns the launch's workgroups: the chunk checks, the table's end, the waves
+uint32_t window_launch_args(WinArgs &wa, const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
+                            void *dst, const WinRect &r, uint32_t *status, const IxTable &ix);
+// the launches of a batch (one, unless the waves exceed WIN_LAUNCH_WAVES: window_batch_plan's prefixes start again there); ba.d is filled,
+// launch(ba, grid) makes one
+template <class Launch>
+inline void window_batch_launches(WinBatchArgs &ba, const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
+                                  uint32_t *d_status, Launch launch) {
+    const WinDesc *h = (const WinDesc *)h_descs;
+    for (size_t first = 0; first < n;) {
+        size_t end = first + 1;
+        while (end < n && h[end].wave0 != 0) end++;
+        const uint64_t waves = (uint64_t)h[end - 1].wave0 + h[end - 1].nwaves;
+        ba.wins = (const WinDesc *)d_descs + first; ba.wstatus = d_status + 1 + first; ba.nwin = (uint32_t)(end - first);
+        ba.chunks = d_chunks; ba.chk_n = first ? 0 : (uint32_t)nchunks; ba.tail = first ? 0 : 1;
+        launch(ba, dim3((uint32_t)(ba.chk_n + ba.tail + (waves + 3) / 4)));
+        first = end;
+    }
+}
 
 // position of the table's last entry against the stream's length: a stream that ends before its last segment starts was cut short
 __device__ __forceinline__ void ix_tail_check(const DecArgs &a) {

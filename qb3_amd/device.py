@@ -123,6 +123,11 @@ class DeviceDecoder:
             raise RuntimeError(f"qb3x_decode_window_device failed: {last_error()}")
         return out.view(-1)[:nbytes].view(getattr(torch, NP_DTYPE[dt])).view(h, w, self.bands)
 
+    def set_window_kernels(self, mask):
+        """qb3x_set_decoder_window_kernels: rasters beyond the 8-bit ones whose window calls take a window kernel (path 1) --
+        qb3_amd.QB3X_WINK_U16: 16-bit rasters of 1, 2, 3, 4, 6, 8 bands with a level-2 table; 0 (the default): none"""
+        lib.qb3x_set_decoder_window_kernels(self.p, int(mask))
+
     def decode_windows(self, d_stream, rects, out=None, index=None):
         """the windows (x0, y0, w, h) of `rects` in ONE call (qb3x_decode_windows_device): a list of device tensors of shape
         (h, w, bands) and the raster's type.  out: a list of contiguous uint8 device tensors, one a window, of at least the

@@ -4,6 +4,8 @@ the whole qb3x_decode_device into a buffer of its own, then a strided device cop
 block rows + crop, path 2); windows of 256^2, 1024^2, 4096^2 and the whole raster at an origin that is not a multiple of 256.
 Events on the caller's stream around N calls, both ways alternating in the same run; the window kernel's own time from the
 library's profile (dec_window) in a pass of its own.  One JSON line per window.
+--kernels16 sets QB3X_WINK_U16 on the handle (qb3x_set_decoder_window_kernels): 16-bit rasters then take the window kernel too
+(path 1, profile name dec_window16); CASE may also be u16x1 (8192 x 8192 x 1 uint16, FTL).
 Without CASE every raster runs in a child process of its own under a time limit, and the first failure ends the run.
 
 tools/window_bench.py --batch [CASE] -- the batch call (qb3x_decode_windows_device) against the same windows through single calls on
@@ -23,7 +25,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-CASES = {"headline": (16384, 16384, 3, 0, "NOISY3", 8), "config3": (8192, 8192, 8, 2, "LANDSAT16", 8)}
+CASES = {"headline": (16384, 16384, 3, 0, "NOISY3", 8), "config3": (8192, 8192, 8, 2, "LANDSAT16", 8), "u16x1": (8192, 8192, 1, 2, "LANDSAT16", 8)}
 
 
 def timed(fn, n):
@@ -39,9 +41,9 @@ def timed(fn, n):
     return a.elapsed_time(b) / n
 
 
-def run(case):
+def run(case, kernels16=False):
     import torch
-    from qb3_amd import synth, device as qdev, TYPESIZE
+    from qb3_amd import synth, device as qdev, TYPESIZE, QB3X_WINK_U16
     w, h, b, dt, gen, mode = CASES[case]
     tsz = TYPESIZE[dt]
     img = synth.generate(w, h, b, dt, gen, 3)
@@ -49,6 +51,7 @@ def run(case):
     enc = qdev.DeviceEncoder(w, h, b, dt, mode=mode, want_index=False, index_chunk=2)
     dst, n, _ = enc.encode(raw)
     dec = qdev.DeviceDecoder(dst, n)
+    dec.set_window_kernels(QB3X_WINK_U16 if kernels16 else 0)
     full = torch.empty(raw.numel(), dtype=torch.uint8, device="cuda")
     rows = full.view(h, w * b * tsz)
     x0, y0 = 1001, 517
@@ -80,8 +83,8 @@ def run(case):
         torch.cuda.synchronize()
         qdev.profile_enable(0)
         prof = qdev.profile_report()
-        kern = {k: round(v[0] / v[1], 4) for k, v in prof.items() if k in ("dec_window", "dec_units")}
-        print(json.dumps({"case": case, "window": [wx, wy, ww, hh], "path": path, "segments": segs, "window_ms": [round(t, 4) for t in t_win],
+        kern = {k: round(v[0] / v[1], 4) for k, v in prof.items() if k in ("dec_window", "dec_window16", "dec_units")}
+        print(json.dumps({"case": case, "kernels16": kernels16, "window": [wx, wy, ww, hh], "path": path, "segments": segs, "window_ms": [round(t, 4) for t in t_win],
                           "decode_and_crop_ms": [round(t, 4) for t in t_old], "kernel_ms": kern}), flush=True)
 
 
@@ -186,6 +189,8 @@ def run_ranged(path, rect=None):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
+    k16 = "--kernels16" in args
+    args = [a for a in args if a != "--kernels16"]
     if args and args[0] == "--ranged":
         if len(args) < 2:
             sys.exit("window_bench: --ranged takes a file (and, optionally, x0,y0,w,h)")
@@ -199,9 +204,9 @@ if __name__ == "__main__":
                 if r.returncode:
                     sys.exit("window_bench: %s ended with status %d; nothing more is run" % (case, r.returncode))
     elif args:
-        run(args[0])
+        run(args[0], k16)
     else:
-        for case in CASES:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), case], timeout=420)
+        for case in ("headline", "config3"):
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), case] + (["--kernels16"] if k16 else []), timeout=420)
             if r.returncode:
                 sys.exit("window_bench: %s ended with status %d; nothing more is run" % (case, r.returncode))
