@@ -282,9 +282,9 @@ class RangedReader:
     """qb3x_open_ranged: windows of a container that is NOT in memory -- a file, or anything a callable reads byte ranges of --
     fetching only the table chunks and the pieces of the stream that hold the rectangles (include/qb3x.h).  `source`: a path, or a
     callable (offset, size) -> bytes-like of exactly `size` bytes (then `size` is the container's size).  last_bytes / last_reads:
-    what the last call asked of the source; last_windows: the path every window of it came by."""
+    what the last call asked of the source; last_windows: the path every window of it came by.  window_kernels: set_window_kernels."""
 
-    def __init__(self, source, size=None):
+    def __init__(self, source, size=None, window_kernels=0):
         import numpy as np
         self._file = None
         if callable(source):
@@ -317,6 +317,13 @@ class RangedReader:
         self.dtype = lib.qb3_get_type(self.p)
         self.last_bytes = self.last_reads = 0
         self.last_windows = []
+        if window_kernels:
+            self.set_window_kernels(window_kernels)
+
+    def set_window_kernels(self, mask):
+        """qb3x_set_decoder_window_kernels on the ranged handle: QB3X_WINK_U16 -- 16-bit rasters of 1, 2, 3, 4, 6, 8 bands with a
+        level-2 table are read in pieces too (else they are read whole, every call); 0 (the default): none"""
+        lib.qb3x_set_decoder_window_kernels(self.p, int(mask))
 
     def set_gap(self, nbytes):
         lib.qb3x_set_ranged_gap(self.p, nbytes)
@@ -355,6 +362,6 @@ class RangedReader:
         self.close()
 
 
-def open_ranged(path_or_callable, size=None):
-    """a RangedReader over a file or a callable (offset, size) -> bytes"""
-    return RangedReader(path_or_callable, size)
+def open_ranged(path_or_callable, size=None, window_kernels=0):
+    """a RangedReader over a file or a callable (offset, size) -> bytes; window_kernels: RangedReader.set_window_kernels"""
+    return RangedReader(path_or_callable, size, window_kernels)

@@ -1,7 +1,8 @@
 // qb3_amd/csrc/api_ranged.cpp -- ranged window reads (include/qb3x.h: qb3x_open_ranged, qb3x_read_windows_ranged,
 // qb3x_decode_windows_ranged): windows of a container that is read through a function of the caller's, fetching only the table chunks
-// and the pieces of the stream that hold the rectangles.  The rules of what is read are stated in qb3x.h; the kernel that decodes from
-// the pieces is k_dec_wins_ranged.hip; everything the shortcut does not take goes, with the whole container, the way of api_window.cpp.
+// and the pieces of the stream that hold the rectangles.  The rules of what is read are stated in qb3x.h; the kernels that decode from
+// the pieces are k_dec_wins_ranged.hip (8-bit rasters) and k_dec_wins16_ranged.hip (16-bit ones, on a handle that asked: QB3X_WINK_U16);
+// everything the shortcut does not take goes, with the whole container, the way of api_window.cpp.
 #include <new>
 #include "qb3_host.h"
 
@@ -33,15 +34,18 @@ struct Chunks {
     size_t size(uint32_t c) const { return IX_HEAD + (size_t)entries(c) * E + IX_PAD + (c + 1 == count ? 2 : 0); }
 };
 
-// does the shortcut take this handle's raster and table (pure: no device, no reader)
-bool ranged_shortcut(const decs *p, Geometry &g, DecPlan &plan, IxTable &ixt, Chunks &ch) {
-    if (p->mode == QB3M_STORED || p->xsize < 4 || p->ysize < 4 || !p->ix_K || !p->ix_bl || p->ix_ver < 3 || !p->ix_pads || is_rle_mode(p->mode)) return false;
+// does the shortcut take this handle's raster and table, and with which kernels (pure: no device, no reader)
+enum class Shortcut { none, u8, u16 };
+Shortcut ranged_shortcut(const decs *p, Geometry &g, DecPlan &plan, IxTable &ixt, Chunks &ch) {
+    if (p->mode == QB3M_STORED || p->xsize < 4 || p->ysize < 4 || !p->ix_K || !p->ix_bl || p->ix_ver < 3 || !p->ix_pads || is_rle_mode(p->mode)) return Shortcut::none;
     g = decoder_geometry(p, p->xsize, p->ysize, 0);
     plan = plan_decode(g);
     ixt = handle_table(p, (const uint8_t *)p);          // (the table is not in device memory: the base only has to be non-null)
-    if (!decode_window_ok(g, plan, ixt)) return false;
+    const Shortcut family = decode_window_ok(g, plan, ixt) ? Shortcut::u8
+                          : (p->win_kernels & QB3X_WINK_U16) && decode_window16_ok(g, plan, ixt) ? Shortcut::u16 : Shortcut::none;
+    if (family == Shortcut::none) return family;
     ch.off = p->ix_off; ch.K = p->ix_K; ch.N = p->ix_per_chunk; ch.E = p->ix_E; ch.count = (uint32_t)ix_chunks(ixt);
-    return ch.at(ch.count - 1) + ch.size(ch.count - 1) <= p->rg_size;
+    return ch.at(ch.count - 1) + ch.size(ch.count - 1) <= p->rg_size ? family : Shortcut::none;
 }
 
 struct BlockRect { uint32_t bx0, bx1, by0, by1; };
@@ -54,7 +58,7 @@ void chunk_list(const Geometry &g, const Chunks &ch, const qb3x_window *wins, si
     chunks.clear();
     for (size_t i = 0; i < n; i++) {
         const BlockRect b = block_rect(g, wins[i]);
-        const uint64_t first = ((uint64_t)b.by0 * g.nbx + b.bx0) / 64, last = std::min<uint64_t>(((uint64_t)b.by1 * g.nbx + b.bx1) / 64 + 1, ch.K - 1);
+        const uint64_t first = ((uint64_t)b.by0 * g.nbx + b.bx0) / g.seg_blocks, last = std::min<uint64_t>(((uint64_t)b.by1 * g.nbx + b.bx1) / g.seg_blocks + 1, ch.K - 1);
         for (uint64_t c = first / ch.N; c <= last / ch.N; c++) chunks.push_back((uint32_t)c);
     }
     chunks.push_back((ch.K - 1) / ch.N);
@@ -153,10 +157,11 @@ size_t stored_windows(decsp p, const qb3x_window *wins, size_t n, uint8_t *paths
 }
 
 // The shortcut.  Marks the windows it gave their pixels (paths[i] = 1) and counts their segments.  1: went through (fall back for the
-// windows that are left); 0: the table is not to be trusted, nothing was written; -1: the call failed (p->error is set)
+// windows that are left); 0: the table is not to be trusted, nothing was written; -1: the call failed (p->error is set).  wide: a
+// 16-bit raster (Shortcut::u16) -- its own blocks per segment (g.seg_blocks), its value size, its kernels; all else is one code
 int pieces_windows(decsp p, const Geometry &g, const DecPlan &plan, const IxTable &ixt, const Chunks &ch, const qb3x_window *wins, size_t n,
-                   uint8_t *paths, size_t *segs, bool host, hipStream_t st) {
-    const size_t tsz = 1, pix = p->nbands * tsz;
+                   uint8_t *paths, size_t *segs, bool host, hipStream_t st, bool wide) {
+    const size_t tsz = szof(p->type), pix = p->nbands * tsz;
     const uint64_t csize = p->rg_size, off = (uint64_t)(p->s_in - p->s_start), base = off & ~(uint64_t)3, in_bits = (uint64_t)p->s_size * 8;
     const uint32_t in_bit0 = (uint32_t)(8 * (off & 3));
     // stage 1: the table chunks the windows' entries are in
@@ -176,7 +181,7 @@ int pieces_windows(decsp p, const Geometry &g, const DecPlan &plan, const IxTabl
     std::vector<std::pair<uint32_t, uint32_t>> runs;    // [first, end)
     for (size_t i = 0; i < n; i++) {
         const BlockRect b = block_rect(g, wins[i]);
-        for (uint64_t by = b.by0; by <= b.by1; by++) runs.emplace_back((uint32_t)((by * g.nbx + b.bx0) / 64), (uint32_t)((by * g.nbx + b.bx1) / 64 + 1));
+        for (uint64_t by = b.by0; by <= b.by1; by++) runs.emplace_back((uint32_t)((by * g.nbx + b.bx0) / g.seg_blocks), (uint32_t)((by * g.nbx + b.bx1) / g.seg_blocks + 1));
     }
     std::sort(runs.begin(), runs.end());
     size_t m = 0;
@@ -185,8 +190,9 @@ int pieces_windows(decsp p, const Geometry &g, const DecPlan &plan, const IxTabl
         else runs[++m] = runs[i];
     }
     runs.resize(m + 1);
-    // a piece per run whose two ends make sense: inside the stream, no longer than its segments can be (a table that says otherwise is
-    // not this stream's; the waves of such a run find no piece and raise their window's status)
+    // a piece per run whose two ends make sense: inside the stream, no longer than its segments can be (px_cap_dw: the worst-case
+    // segment of either family; a table that says otherwise is not this stream's; the waves of such a run find no piece and raise
+    // their window's status)
     struct Span { uint64_t a, b; size_t at; };         // container bytes [a, b); at: where they start in the packed words (bytes)
     std::vector<Piece> pieces;
     std::vector<Span> spans;
@@ -267,7 +273,7 @@ int pieces_windows(decsp p, const Geometry &g, const DecPlan &plan, const IxTabl
     hipError_t e = hipMemcpyAsync(p->d_rg.p, up, upbytes - 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_status, 0, stbytes, st);
     if (e != hipSuccess) return hip_fail("ranged windows: upload", e);
-    if (launch_decode_windows_ranged(g, plan, in_bit0, in_bits, up, d_up, n, d_up + dbytes, pieces.size(), d_up + dbytes + pbytes,
+    if ((wide ? launch_decode_windows16_ranged : launch_decode_windows_ranged)(g, plan, in_bit0, in_bits, up, d_up, n, d_up + dbytes, pieces.size(), d_up + dbytes + pbytes,
                                      (const uint32_t *)(d_up + dbytes + pbytes + ebytes), d_status, st, ixt)) return hip_fail("ranged windows: launch", hipSuccess);
     e = hipMemcpyAsync(p->h_wst.p, d_status, stbytes, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = wait_stream(st);
@@ -304,8 +310,12 @@ size_t ranged_call(decsp p, const qb3x_window *wins, size_t n, bool host, hipStr
     IxTable ixt;
     Chunks ch;
     size_t segs = 0;
-    if (ranged_shortcut(p, g, plan, ixt, ch)) {
-        const int went = pieces_windows(p, g, plan, ixt, ch, wins, n, paths, &segs, host, st);
+    Shortcut family = ranged_shortcut(p, g, plan, ixt, ch);
+    // the 16-bit kernels store halfwords: one device destination on an odd address and the call goes windows_device's way, which
+    // applies the same test (host destinations are decoded into the handle's buffer, every window on a dword)
+    for (size_t i = 0; family == Shortcut::u16 && !host && i < n; i++) if ((uintptr_t)wins[i].dst & 1) family = Shortcut::none;
+    if (family != Shortcut::none) {
+        const int went = pieces_windows(p, g, plan, ixt, ch, wins, n, paths, &segs, host, st, family == Shortcut::u16);
         trim_cache(p);
         if (went < 0) return 0;
     }
@@ -420,7 +430,7 @@ QB3_API size_t qb3x_ranged_table_ranges(const decsp p, const qb3x_window *wins, 
         DecPlan plan;
         IxTable ixt;
         Chunks ch;
-        if (!ranged_shortcut(p, g, plan, ixt, ch)) return 0;
+        if (ranged_shortcut(p, g, plan, ixt, ch) == Shortcut::none) return 0;
         std::vector<uint32_t> chunks;
         chunk_list(g, ch, wins, n, chunks);
         for (size_t i = 0; out && i < chunks.size() && i < cap; i++) out[i] = qb3x_range{ ch.at(chunks[i]), ch.size(chunks[i]) };

@@ -63,31 +63,6 @@ bool decode_window16_ok(const Geometry &g, const DecPlan &plan, const IxTable &i
     return decode_strips_ok(g, plan, ix) && aligned_dec_kernel(g, plan) == DecKernel::px16 && ix.block_lens && ix.version >= 3 && g.nblocks < (1ull << 31);
 }
 
-// one place names the instantiations: KERNEL<BG, RGB, ORDER, STEP> by the plan's bands per lane and band map, the raster's order and mode
-#define QB3_WIN16_DISPATCH(KERNEL, args)                                                                                              \
-    do {                                                                                                                              \
-        const bool step = g.mode != CM_FTL, z = g.order == ZCURVE;                                                                    \
-        auto go = [&](auto bgc, auto rgbc) {                                                                                          \
-            constexpr int BG = decltype(bgc)::value;                                                                                  \
-            constexpr bool RGB = decltype(rgbc)::value;                                                                               \
-            if (!z && !step) hipLaunchKernelGGL((KERNEL<BG, RGB, HILBERT, false>), grid, dim3(256), plan.lds_px, st, args);           \
-            else if (!z && step) hipLaunchKernelGGL((KERNEL<BG, RGB, HILBERT, true>), grid, dim3(256), plan.lds_px, st, args);        \
-            else if (z && !step) hipLaunchKernelGGL((KERNEL<BG, RGB, ZCURVE, false>), grid, dim3(256), plan.lds_px, st, args);        \
-            else hipLaunchKernelGGL((KERNEL<BG, RGB, ZCURVE, true>), grid, dim3(256), plan.lds_px, st, args);                         \
-        };                                                                                                                            \
-        using T = std::true_type; using F = std::false_type;                                                                          \
-        switch (plan.px16_bg) {                                                                                                       \
-        case 1: go(std::integral_constant<int, 1>(), F()); break;                                                                     \
-        case 2: go(std::integral_constant<int, 2>(), F()); break;                                                                     \
-        case 3: if (plan.px_rgb) go(std::integral_constant<int, 3>(), T()); else go(std::integral_constant<int, 3>(), F()); break;    \
-        default: if (plan.px_rgb) go(std::integral_constant<int, 4>(), T()); else go(std::integral_constant<int, 4>(), F()); break;   \
-        }                                                                                                                             \
-    } while (0)
-
-static void window16_dec_args(DecArgs &a, const DecPlan &plan) {       // what dec_px16_kernel's lanes take besides window_dec_args
-    a.px_ng = plan.px16_ng; a.px_magic_ng = magic_div(a.px_ng); a.in_cap_full = plan.px_cap_dw;
-}
-
 int launch_decode_window16(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
                            void *dst, const WinRect &r, uint32_t *status, void *stream, const IxTable &ix) {
     hipStream_t st = (hipStream_t)stream;

@@ -14,14 +14,6 @@
 
 namespace qb3dev {
 
-struct WinRangedArgs {
-    DecArgs d;                      // geometry, stream length, staging capacity, entry size; d.in32 and d.ix are not used
-    const WinDesc *wins;            // the launch's windows, wave0 counted from the launch's first window
-    uint32_t *wstatus;              // ... their status words
-    WinSrcPieces src;               // pieces, entries, packed words
-    uint32_t nwin;
-};
-
 template <int B, bool RGB, uint64_t ORDER, bool STEP>
 __global__ void __launch_bounds__(256) dec_wins_ranged_kernel(const WinRangedArgs ra) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -52,26 +44,20 @@ int launch_decode_windows_ranged(const Geometry &g, const DecPlan &plan, uint32_
                                  uint32_t *d_status, void *stream, const IxTable &ix) {
     hipStream_t st = (hipStream_t)stream;
     if (!decode_window_ok(g, plan, ix) || !n || !npieces || npieces > 0xffffffffull) { set_error("ranged window batch: not for this raster", 0); return -1; }
-    const WinDesc *h = (const WinDesc *)h_descs;
     WinRangedArgs ra = {};
     IxTable none = ix;
     none.base = nullptr;            // (the table is not in device memory)
     window_dec_args(ra.d, g, plan, nullptr, in_bit0, in_bits, d_status, none);
     ra.src.pieces = (const WinPiece *)d_pieces; ra.src.npieces = (uint32_t)npieces;
     ra.src.ents = (const uint8_t *)d_entries; ra.src.words = d_words;
-    for (size_t first = 0; first < n;) {                // one launch, unless the waves exceed WIN_LAUNCH_WAVES (window_batch_plan's prefixes)
-        size_t end = first + 1;
-        while (end < n && h[end].wave0 != 0) end++;
-        const uint64_t waves = (uint64_t)h[end - 1].wave0 + h[end - 1].nwaves;
-        ra.wins = (const WinDesc *)d_descs + first; ra.wstatus = d_status + 1 + first; ra.nwin = (uint32_t)(end - first);
-        const dim3 grid((uint32_t)((waves + 3) / 4));
+    // one launch, unless the waves exceed WIN_LAUNCH_WAVES (window_batch_plan's prefixes)
+    window_ranged_launches(ra, h_descs, d_descs, n, d_status, [&](const WinRangedArgs &ra, dim3 grid) {
         ProfScope ps("dec_window_ranged", st);
         if (g.bands == 1) launch_dec_wins_ranged_b<1, false>(ra, grid, plan.lds_px, st);
         else if (g.bands == 3) { if (plan.px_rgb) launch_dec_wins_ranged_b<3, true>(ra, grid, plan.lds_px, st); else launch_dec_wins_ranged_b<3, false>(ra, grid, plan.lds_px, st); }
         else { if (plan.px_rgb) launch_dec_wins_ranged_b<4, true>(ra, grid, plan.lds_px, st); else launch_dec_wins_ranged_b<4, false>(ra, grid, plan.lds_px, st); }
-        HIPCHK(hipGetLastError());
-        first = end;
-    }
+    });
+    HIPCHK(hipGetLastError());
     return 0;
 }
 

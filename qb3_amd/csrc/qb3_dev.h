@@ -303,6 +303,11 @@ constexpr size_t WIN_PIECE_BYTES = 32;
 int launch_decode_windows_ranged(const Geometry &g, const DecPlan &plan, uint32_t in_bit0, uint64_t in_bits, const void *h_descs, const void *d_descs,
                                  size_t n, const void *d_pieces, size_t npieces, const void *d_entries, const uint32_t *d_words,
                                  uint32_t *d_status, void *stream, const IxTable &ix);
+// ... and of a 16-bit raster the 16-bit window kernels take (k_dec_wins16_ranged.hip; decode_window16_ok): the same arguments, the
+// raster's own blocks per segment, every destination halfword aligned
+int launch_decode_windows16_ranged(const Geometry &g, const DecPlan &plan, uint32_t in_bit0, uint64_t in_bits, const void *h_descs, const void *d_descs,
+                                   size_t n, const void *d_pieces, size_t npieces, const void *d_entries, const uint32_t *d_words,
+                                   uint32_t *d_status, void *stream, const IxTable &ix);
 
 // Reindex (k_reindex.hip): the table chunks this library's encoder writes for a raster, made from the index a plain walk of its stream
 // has rebuilt (launch_decode with index == nullptr leaves it in ws behind the status words), and the new container around them.

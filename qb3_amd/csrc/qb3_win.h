@@ -131,6 +131,28 @@ struct WinSrcPieces {
         return words[pc.word0 + (uint32_t)(w - ((uint64_t)pc.sw0_hi << 32 | pc.sw0_lo))];      // (behind the container's end a piece has no words: holds() said no)
     }
 };
+// what the ranged kernels take (dec_wins_ranged_kernel, dec_wins16_ranged_kernel)
+struct WinRangedArgs {
+    DecArgs d;                      // geometry, stream length, staging capacity, entry size; d.in32 and d.ix are not used
+    const WinDesc *wins;            // the launch's windows, wave0 counted from the launch's first window
+    uint32_t *wstatus;              // ... their status words
+    WinSrcPieces src;               // pieces, entries, packed words
+    uint32_t nwin;
+};
+// the launches of a ranged batch, split as window_batch_launches splits; no check workgroups (the host verified the chunks); ra.d and
+// ra.src are filled, launch(ra, grid) makes one
+template <class Launch>
+inline void window_ranged_launches(WinRangedArgs &ra, const void *h_descs, const void *d_descs, size_t n, uint32_t *d_status, Launch launch) {
+    const WinDesc *h = (const WinDesc *)h_descs;
+    for (size_t first = 0; first < n;) {
+        size_t end = first + 1;
+        while (end < n && h[end].wave0 != 0) end++;
+        const uint64_t waves = (uint64_t)h[end - 1].wave0 + h[end - 1].nwaves;
+        ra.wins = (const WinDesc *)d_descs + first; ra.wstatus = d_status + 1 + first; ra.nwin = (uint32_t)(end - first);
+        launch(ra, dim3((uint32_t)((waves + 3) / 4)));
+        first = end;
+    }
+}
 
 // Wave `wid` of window w (wave: its number in the workgroup of four; both wave uniform): the k-th segment of one of the window's block
 // rows, decoded as dec_px_kernel's BL branch does, stored where the window's blocks go.  status: the word this window's failures go to.

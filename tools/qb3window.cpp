@@ -1,10 +1,12 @@
 // tools/qb3window.cpp -- a rectangle of a QB3 file as a PNM image, reading only the bytes of the file that hold it: the command line
 // caller of qb3x_open_ranged / qb3x_read_windows_ranged (include/qb3x.h), with pread as the reader.  A file with a level-2 restart
-// table (cqb3x with QB3X_INDEX_CHUNK=2, qb3index -2) is read in pieces; any other file is read whole and gives the same pixels.
+// table (cqb3x with QB3X_INDEX_CHUNK=2, qb3index -2) is read in pieces -- an 8-bit one always, a 16-bit one with -k; any other file
+// is read whole and gives the same pixels.
 //
-//   qb3window [-v] [-g gap] in.qb3 x0,y0,w,h out.pnm
+//   qb3window [-v] [-k] [-g gap] in.qb3 x0,y0,w,h out.pnm
 //
 //   -g gap  merge two byte ranges that lie at most `gap` bytes apart (fewer reads, more bytes; default 0)
+//   -k      16-bit files too are read in pieces (qb3x_set_decoder_window_kernels, QB3X_WINK_U16)
 //   -v      prints bytes read and calls of the reader against the file's size
 #include "qb3x.h"
 #include <cstdint>
@@ -18,7 +20,7 @@
 
 namespace {
 
-const char *USAGE = "qb3window [-v] [-g gap] in.qb3 x0,y0,w,h out.pnm\n";
+const char *USAGE = "qb3window [-v] [-k] [-g gap] in.qb3 x0,y0,w,h out.pnm\n";
 
 int fail(const std::string &msg) {
     fprintf(stderr, "qb3window: %s\n", msg.c_str());
@@ -40,12 +42,13 @@ int read_at(void *ctx, uint64_t offset, void *dst, size_t size) {
 }  // namespace
 
 int main(int argc, char **argv) {
-    bool verbose = false;
+    bool verbose = false, kernels16 = false;
     size_t gap = 0;
     std::vector<std::string> names;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "-v") verbose = true;
+        else if (a == "-k") kernels16 = true;
         else if (a == "-g" && i + 1 < argc) gap = (size_t)strtoull(argv[++i], nullptr, 10);
         else if (!a.empty() && a[0] == '-') { fputs(USAGE, stderr); return 2; }
         else names.push_back(a);
@@ -67,6 +70,7 @@ int main(int argc, char **argv) {
         std::vector<uint8_t> pix(w * h * dims[2] * tsz);
         const qb3x_window win = { (size_t)x0, (size_t)y0, (size_t)w, (size_t)h, pix.data(), 0 };
         qb3x_set_ranged_gap(d, gap);
+        if (kernels16) qb3x_set_decoder_window_kernels(d, QB3X_WINK_U16);
         if (qb3x_read_windows_ranged(d, &win, 1) != 1) ret = fail(std::string("the window was not read: ") + qb3x_last_error());
         else {
             if (tsz == 2) for (size_t i = 0; i + 1 < pix.size(); i += 2) std::swap(pix[i], pix[i + 1]);     // PNM samples are big endian

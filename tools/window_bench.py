@@ -17,7 +17,11 @@ own.  One JSON line per case.
 tools/window_bench.py --ranged FILE [x0,y0,w,h] -- a window of a file on disk read in pieces (qb3x_open_ranged over os.pread,
 qb3x_read_windows_ranged) against qb3x_read_window of the same file read whole: wall-clock milliseconds (the reads are part of the
 work) of a cold window (a fresh handle a call), a warm one (the table chunks cached in the handle) and the whole-file way, the best of
-a few, with the bytes read beside each.  The window defaults to 512 x 512 in the raster's middle.  One JSON line."""
+a few, with the bytes read beside each.  The window defaults to 512 x 512 in the raster's middle.  One JSON line.
+--kernels16 sets QB3X_WINK_U16 on the ranged handles: a 16-bit file is then read in pieces too (without it: whole, every call), and
+the line also carries the kernel's own time (dec_window16_ranged, from the library's profile in a pass of its own).
+
+tools/window_bench.py --write CASE FILE -- writes CASE's container (level-2 table) to FILE, for --ranged to read."""
 import json
 import os
 import subprocess
@@ -145,10 +149,22 @@ def run_batch(case):
                       "ratio": round(min(t_batch) / min(t_single), 4), "kernel_ms": kern, "launches_per_call": launches}), flush=True)
 
 
-def run_ranged(path, rect=None):
+def write_case(case, path):
+    import torch
+    from qb3_amd import synth, device as qdev
+    w, h, b, dt, gen, mode = CASES[case]
+    img = synth.generate(w, h, b, dt, gen, 3)
+    enc = qdev.DeviceEncoder(w, h, b, dt, mode=mode, want_index=False, index_chunk=2)
+    dst, n, _ = enc.encode(img.reshape(-1).view(torch.uint8))
+    dst[:n].cpu().numpy().tofile(path)
+    print(json.dumps({"case": case, "file": os.path.basename(path), "file_bytes": n}), flush=True)
+
+
+def run_ranged(path, rect=None, kernels16=False):
     import time
     import numpy as np
     import qb3_amd
+    mask = qb3_amd.QB3X_WINK_U16 if kernels16 else 0
     size = os.path.getsize(path)
     with qb3_amd.open_ranged(path) as rd:
         W, H = rd.width, rd.height
@@ -166,7 +182,7 @@ def run_ranged(path, rect=None):
         return best, out
 
     def cold():
-        with qb3_amd.open_ranged(path) as rd:
+        with qb3_amd.open_ranged(path, window_kernels=mask) as rd:
             return rd.read_windows([rect])[0], rd.last_bytes, rd.last_reads, rd.last_windows[0]
 
     def whole():
@@ -176,15 +192,24 @@ def run_ranged(path, rect=None):
     t_whole, want = wall(whole)
     t_cold, (got, cold_bytes, cold_reads, path1) = wall(cold)
     assert np.array_equal(got, want), "the ranged window is not the window of the whole file"
-    with qb3_amd.open_ranged(path) as rd:
+    kern = {}
+    with qb3_amd.open_ranged(path, window_kernels=mask) as rd:
         rd.read_windows([rect])
         t_warm, got = wall(lambda: rd.read_windows([rect])[0])
         warm_bytes, warm_reads = rd.last_bytes, rd.last_reads
+        if kernels16:                                   # the kernel's own time, in a pass of its own
+            from qb3_amd import device as qdev
+            qdev.profile_reset()
+            qdev.profile_enable(1)
+            for _ in range(20):
+                rd.read_windows([rect])
+            qdev.profile_enable(0)
+            kern = {k: round(v[0] / v[1], 4) for k, v in qdev.profile_report().items() if k in ("dec_window16_ranged", "dec_window_ranged")}
     assert np.array_equal(got, want)
-    print(json.dumps({"file": os.path.basename(path), "file_bytes": size, "raster": [W, H], "window": list(rect), "path": path1,
+    print(json.dumps({"file": os.path.basename(path), "file_bytes": size, "raster": [W, H], "window": list(rect), "kernels16": kernels16, "path": path1,
                       "cold_ms": round(t_cold, 3), "cold_bytes": cold_bytes, "cold_reads": cold_reads,
                       "warm_ms": round(t_warm, 3), "warm_bytes": warm_bytes, "warm_reads": warm_reads,
-                      "whole_file_ms": round(t_whole, 3), "whole_file_bytes": size}), flush=True)
+                      "whole_file_ms": round(t_whole, 3), "whole_file_bytes": size, "kernel_ms": kern}), flush=True)
 
 
 if __name__ == "__main__":
@@ -194,7 +219,11 @@ if __name__ == "__main__":
     if args and args[0] == "--ranged":
         if len(args) < 2:
             sys.exit("window_bench: --ranged takes a file (and, optionally, x0,y0,w,h)")
-        run_ranged(args[1], tuple(int(v) for v in args[2].split(",")) if len(args) > 2 else None)
+        run_ranged(args[1], tuple(int(v) for v in args[2].split(",")) if len(args) > 2 else None, k16)
+    elif args and args[0] == "--write":
+        if len(args) != 3 or args[1] not in CASES:
+            sys.exit("window_bench: --write takes a case (%s) and a file" % ", ".join(CASES))
+        write_case(args[1], args[2])
     elif args and args[0] == "--batch":
         if len(args) > 1:
             run_batch(args[1])
