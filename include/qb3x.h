@@ -72,6 +72,13 @@ size_t qb3x_decode_device(decsp p, const void *d_src, void *d_dst, const void *d
  *      bands (FTL / BASE, level-2 table of version 3, d_dst on an even address; else they go as below): the same, with the
  *      raster's blocks per segment (64, 32 for eight bands, 21 for six) -- time follows the window, and a handle that only ever
  *      takes path 1 allocates no scratch raster.  Path, segment count and status are reported with path 1's meaning.
+ *      With QB3X_WINK_CF8 path 1 also takes 8-bit rasters of 1, 3 or 4 bands in the common-factor modes (QB3M_CF, QB3M_CF_H;
+ *      QB3M_BEST / QB3M_CF_RLE where the RLE0 pass did not win: the header's mode byte says which) whose table, of level 1 or 2,
+ *      carries a field per block (what this library's encoder writes for them; an entry has 6 + 3 * bands + 192 bytes): 64 blocks a
+ *      segment, any destination address, the same reporting.  The factor in force inside a segment is found among the segment's own
+ *      units, before the first of them it is the entry's.  What the kernel cross-checks under a table whose check was sealed again is
+ *      what the whole decode from the table cross-checks: positions, block lengths, entering rungs -- not an entry's entering value
+ *      or factor, which both take as they are and turn into the same pixels.
  *   2  every other raster with a level-2 table (16-bit, 32/64-bit, other band counts, the common-factor modes): the segments of the
  *      window's block ROWS are decoded into a scratch raster the handle owns, then cropped.  Time follows the window's rows; the
  *      scratch is raster sized (qb3_decoded_size bytes of device memory).
@@ -104,9 +111,13 @@ size_t qb3x_last_window_segments(const decsp p);
  * Honoured by qb3x_decode_window_device, qb3x_decode_windows_device, qb3x_read_window and qb3x_read_windows, and on a handle of
  * qb3x_open_ranged by qb3x_read_windows_ranged, qb3x_decode_windows_ranged and qb3x_ranged_table_ranges: with QB3X_WINK_U16 these
  * read a 16-bit raster the kernels take in pieces (below), without it whole.  Unknown bits are ignored; a NULL handle: no-op.  The
- * bytes written are the same with and without a bit: the bit only chooses the way.  Harmless on a handle whose raster the kernels do not take (8-bit data, other band counts, the common-factor
- * modes, STORED containers, narrow images, a level-1 table). */
+ * bytes written are the same with and without a bit: the bit only chooses the way.  Harmless on a handle whose raster the kernels of
+ * the bits set do not take (other value sizes, other band counts, other modes, a container whose RLE0 pass won, STORED containers,
+ * narrow images, a table without block fields, an out-of-band d_index).
+ * QB3X_WINK_CF8 adds NO pieces shortcut on a handle of qb3x_open_ranged: such a file is still read whole, once a call, and its
+ * windows then go through qb3x_decode_windows_device's way, which takes the kernel. */
 #define QB3X_WINK_U16 1u   /* 16-bit rasters of 1, 2, 3, 4, 6, 8 bands, FTL / BASE, level-2 table: window kernel (path 1) instead of strips (path 2); ranged handles: pieces instead of the whole container */
+#define QB3X_WINK_CF8 2u   /* 8-bit rasters of 1, 3, 4 bands in the common-factor modes (QB3M_CF, QB3M_CF_H; QB3M_BEST / QB3M_CF_RLE where the RLE0 pass did not win), table with block fields: window kernel (path 1) instead of strips (path 2) */
 void qb3x_set_decoder_window_kernels(decsp p, unsigned mask);
 
 /* A batch of windows: n rectangles of ONE raster in one call -- what a tile server, a viewer or a cropping loader asks of a raster
@@ -329,7 +340,7 @@ size_t qb3_decode(decsp p, void *destination);                                  
  * events on the launch stream; totals are resolved at the library's own synchronisation points.
  * Kernel names: enc_units, enc_scan, enc_concat, enc_seams, enc_best_units, enc_best_scan, enc_best_recode,
  * dec_index_table, dec_index_serial, dec_index_prev, dec_index_scan, dec_units, dec_segments, dec_window (the window kernel of
- * qb3x_decode_window_device, path 1), dec_window16 (the 16-bit window kernels: path 1 under QB3X_WINK_U16), dec_window_ranged (the same from fetched pieces: the ranged calls), dec_window16_ranged (... of 16-bit rasters under QB3X_WINK_U16), reindex_fill, reindex_finish (qb3x_reindex_device: the table's entries; everything else of the
+ * qb3x_decode_window_device, path 1), dec_window16 (the 16-bit window kernels: path 1 under QB3X_WINK_U16), dec_window_best (the window kernels of the 8-bit common-factor modes: path 1 under QB3X_WINK_CF8), dec_window_ranged (the same from fetched pieces: the ranged calls), dec_window16_ranged (... of 16-bit rasters under QB3X_WINK_U16), reindex_fill, reindex_finish (qb3x_reindex_device: the table's entries; everything else of the
  * new container).
  * level: 0 off, 1 every kernel, 2 all but the microsecond kernels (enc_scan, enc_seams, enc_best_scan), whose two
  * events cost more than they take. */

@@ -32,6 +32,7 @@ QB3M_BASE_Z, QB3M_CF, QB3M_RLE, QB3M_CF_RLE, QB3M_BASE_H, QB3M_CF_H, QB3M_RLE_H,
 QB3M_DEFAULT, QB3M_BASE, QB3M_BEST, QB3M_STORED, QB3M_INVALID = 8, 4, 7, 255, -1
 QB3X_REF_CBAND0 = 1
 QB3X_WINK_U16 = 1           # qb3x_set_decoder_window_kernels: the 16-bit window kernels
+QB3X_WINK_CF8 = 2           # ... the window kernels of the 8-bit common-factor modes (1, 3, 4 bands)
 TYPESIZE = (1, 1, 2, 2, 4, 4, 8, 8)
 
 _vp, _sz, _u64 = C.c_void_p, C.c_size_t, C.c_uint64
@@ -322,7 +323,8 @@ class RangedReader:
 
     def set_window_kernels(self, mask):
         """qb3x_set_decoder_window_kernels on the ranged handle: QB3X_WINK_U16 -- 16-bit rasters of 1, 2, 3, 4, 6, 8 bands with a
-        level-2 table are read in pieces too (else they are read whole, every call); 0 (the default): none"""
+        level-2 table are read in pieces too (else they are read whole, every call); QB3X_WINK_CF8 -- 8-bit common-factor rasters are
+        still read whole, their windows then take the window kernel; 0 (the default): none"""
         lib.qb3x_set_decoder_window_kernels(self.p, int(mask))
 
     def set_gap(self, nbytes):

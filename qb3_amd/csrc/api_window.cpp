@@ -12,7 +12,8 @@ using namespace qb3api;
 //           straight into the caller's buffer.  The single call's kernel (k_dec_win.hip) takes its window as kernel arguments and
 //           gives one status word; the batch's (k_dec_wins.hip) decodes all windows in ONE launch, a status word per window.
 //           On a handle that asked for them (qb3x_set_decoder_window_kernels, QB3X_WINK_U16) also 16-bit rasters of 1, 2, 3, 4, 6 or
-//           8 bands, through the kernels of k_dec_win16.hip (wide: the flag the two functions below pick their launcher by);
+//           8 bands, through the kernels of k_dec_win16.hip, and (QB3X_WINK_CF8) 8-bit rasters of 1, 3 or 4 bands in the common-factor
+//           modes, through those of k_dec_win_best.hip (WinFamily: what the two functions below pick their launcher by);
 //   path 2  every other raster that decodes strip by strip (decode_strips_ok): the windows' block rows as ranges of segments, merged
 //           so that a segment is decoded once, into the handle's scratch raster, then a crop per window;
 //   path 3  ONE whole decode with its fallback ladder into the scratch raster for all windows that have no pixels yet, then their crops.
@@ -56,12 +57,21 @@ static WinSrc window_source(const decs *p, const Geometry &g, const void *d_src)
                    (uint32_t)(8 * (off & 3)), (uint64_t)p->s_size * 8 };
 }
 
+// the kernels path 1 goes through, and their launchers: the single call's and the batch's
+enum class WinFamily { none, u8, u16, cf8 };
+static const struct {
+    int (*one)(const Geometry &, const DecPlan &, const uint32_t *, uint32_t, uint64_t, void *, const WinRect &, uint32_t *, void *, const IxTable &);
+    int (*batch)(const Geometry &, const DecPlan &, const uint32_t *, uint32_t, uint64_t, const void *, const void *, size_t, const uint32_t *, size_t, uint32_t *, void *, const IxTable &);
+} win_launchers[] = {      // in WinFamily's order
+    { nullptr, nullptr }, { launch_decode_window, launch_decode_windows }, { launch_decode_window16, launch_decode_windows16 },
+    { launch_decode_window_best, launch_decode_windows_best } };
+
 // The three functions below mark the windows they gave their pixels (paths[i]) and count the segments they decoded; false: a HIP failure.
 // path 1, the single call: the window as kernel arguments, one status word back
-static bool window_kernel_one(decsp p, const WinSrc &s, const qb3x_window &w, uint8_t *path, size_t *segs, hipStream_t st, bool wide) {
+static bool window_kernel_one(decsp p, const WinSrc &s, const qb3x_window &w, uint8_t *path, size_t *segs, hipStream_t st, WinFamily fam) {
     const WinRect r = win_rect(p, w);
     uint32_t status = 1;
-    if (!p->d_wst.ensure(64) || (wide ? launch_decode_window16 : launch_decode_window)(s.g, s.plan, s.in32, s.in_bit0, s.in_bits, w.dst, r, (uint32_t *)p->d_wst.p, st, s.ixt)) return false;
+    if (!p->d_wst.ensure(64) || win_launchers[(int)fam].one(s.g, s.plan, s.in32, s.in_bit0, s.in_bits, w.dst, r, (uint32_t *)p->d_wst.p, st, s.ixt)) return false;
     const hipError_t e = fetch_small(&status, p->d_wst.p, 4, st);
     if (e != hipSuccess) { set_error("window kernel", (int)e); return false; }
     *segs = (size_t)window_segments(s.g, r);
@@ -69,7 +79,7 @@ static bool window_kernel_one(decsp p, const WinSrc &s, const qb3x_window &w, ui
     return true;
 }
 // path 1, a batch: descriptors and the chunk list are built in the pinned area, one copy up; n + 1 status words, one memset, one copy back
-static bool window_kernel_batch(decsp p, const WinSrc &s, const qb3x_window *wins, size_t n, uint8_t *paths, size_t *segs, hipStream_t st, bool wide) {
+static bool window_kernel_batch(decsp p, const WinSrc &s, const qb3x_window *wins, size_t n, uint8_t *paths, size_t *segs, hipStream_t st, WinFamily fam) {
     const size_t dbytes = n * WIN_DESC_BYTES, upbytes = dbytes + 4 * ix_chunks(s.ixt), stbytes = 4 * (n + 1);
     if (!p->h_wdesc.ensure(upbytes) || !p->h_wst.ensure(stbytes) || !p->d_wdesc.ensure(upbytes) || !p->d_wst.ensure(stbytes)) return false;
     std::vector<WinRect> rects(n);
@@ -82,7 +92,7 @@ static bool window_kernel_batch(decsp p, const WinSrc &s, const qb3x_window *win
     uint32_t *d_status = (uint32_t *)p->d_wst.p;
     HIPOK(hipMemcpyAsync(p->d_wdesc.p, p->h_wdesc.p, dbytes + 4 * nchunks, hipMemcpyHostToDevice, st));
     if (hipMemsetAsync(d_status, 0, stbytes, st) != hipSuccess) return false;
-    if ((wide ? launch_decode_windows16 : launch_decode_windows)(s.g, s.plan, s.in32, s.in_bit0, s.in_bits, p->h_wdesc.p, p->d_wdesc.p, n,
+    if (win_launchers[(int)fam].batch(s.g, s.plan, s.in32, s.in_bit0, s.in_bits, p->h_wdesc.p, p->d_wdesc.p, n,
                               (const uint32_t *)((const uint8_t *)p->d_wdesc.p + dbytes), nchunks, d_status, st, s.ixt)) return false;
     hipError_t e = hipMemcpyAsync(p->h_wst.p, d_status, stbytes, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = wait_stream(st);
@@ -142,8 +152,11 @@ size_t qb3api::windows_device(decsp p, const void *d_src, const void *d_index, c
         // the 16-bit window kernels: a handle that asked, a raster and table they take, halfword stores to every destination
         bool wide = (p->win_kernels & QB3X_WINK_U16) && decode_window16_ok(g, s.plan, s.ixt);
         for (size_t i = 0; wide && i < n; i++) wide = ((uintptr_t)wins[i].dst & 1) == 0;
-        if (wide || decode_window_ok(g, s.plan, s.ixt)) {
-            if (!(single ? window_kernel_one(p, s, wins[0], paths, &segs, st, wide) : window_kernel_batch(p, s, wins, n, paths, &segs, st, wide))) return fail();
+        // the common-factor window kernels: a handle that asked, a raster and table they take; byte stores, any destination
+        const WinFamily fam = wide ? WinFamily::u16 : decode_window_ok(g, s.plan, s.ixt) ? WinFamily::u8
+                            : (p->win_kernels & QB3X_WINK_CF8) && decode_window_best_ok(g, s.plan, s.ixt) ? WinFamily::cf8 : WinFamily::none;
+        if (fam != WinFamily::none) {
+            if (!(single ? window_kernel_one(p, s, wins[0], paths, &segs, st, fam) : window_kernel_batch(p, s, wins, n, paths, &segs, st, fam))) return fail();
         } else if ((scratch = decode_strips_ok(g, s.plan, s.ixt))) {
             if (!window_strips(p, s, wins, n, paths, &segs, st)) return fail();
         }

@@ -292,6 +292,16 @@ int launch_decode_window16(const Geometry &g, const DecPlan &plan, const uint32_
 int launch_decode_windows16(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
                             const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
                             uint32_t *d_status, void *stream, const IxTable &ix);
+// The window kernels of the 8-bit common-factor modes (k_dec_win_best.hip): rasters of 1, 3 or 4 bands in CM_BEST whose table (level 1
+// or 2) carries the block fields dec_px_best_kernel decodes a segment from alone.  decode_window_best_ok: does the raster and its table
+// qualify (the host also asks the handle's switch, QB3X_WINK_CF8, before it takes them).  The launchers are launch_decode_window's and
+// launch_decode_windows' in everything but the kernels; dst needs no alignment.
+bool decode_window_best_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix);
+int launch_decode_window_best(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
+                              void *dst, const WinRect &r, uint32_t *status, void *stream, const IxTable &ix);
+int launch_decode_windows_best(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
+                               const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
+                               uint32_t *d_status, void *stream, const IxTable &ix);
 // The same from PIECES of the container (k_dec_wins_ranged.hip; api_ranged.cpp fetches them): d_pieces: npieces >= 1 pieces sorted by
 // first segment, each a run of consecutive segments { seg0, nseg, ent0, word0, stream word of its first packed word (low, high),
 // nwords, 0 }; d_entries: the compact array of table entries (ix.entry_bytes each), nseg + 1 per piece from index ent0; d_words: the

@@ -6,13 +6,19 @@ Events on the caller's stream around N calls, both ways alternating in the same 
 library's profile (dec_window) in a pass of its own.  One JSON line per window.
 --kernels16 sets QB3X_WINK_U16 on the handle (qb3x_set_decoder_window_kernels): 16-bit rasters then take the window kernel too
 (path 1, profile name dec_window16); CASE may also be u16x1 (8192 x 8192 x 1 uint16, FTL).
-Without CASE every raster runs in a child process of its own under a time limit, and the first failure ends the run.
+--kernels-cf sets QB3X_WINK_CF8: CASE best (the 16384 x 16384 x 3 QB3M_BEST raster of bench.py's second configuration) then takes the
+window kernel of the common-factor modes (path 1, profile name dec_window_best).  The same call with and without the bit alternate
+in one run (window_ms against window_off_ms: the strips of path 2), and the profile pass also times the whole decode's kernel
+(dec_units) for the whole-raster window to be compared with.
+Without CASE every raster runs in a child process of its own under a time limit, and the first failure ends the run; --kernels-cf
+then adds CASE best and is passed to it alone (the bit changes nothing for the other two).
 
 tools/window_bench.py --batch [CASE] -- the batch call (qb3x_decode_windows_device) against the same windows through single calls on
 the same handle: 64 windows of 256^2 and 64 of 1024^2 of the headline raster at seeded random origins that are not multiples of 256
 (path 1: one launch against 64), and 16 windows of 256^2 of a plain 4096 x 4096 x 3 container (path 3: one whole decode against
 16).  Same timing: events on the caller's stream, alternating over three rounds in one process, dec_window's time in a pass of its
-own.  One JSON line per case.
+own.  One JSON line per case.  With --kernels-cf the cases are best256 and best1024 (the QB3M_BEST raster): the batch with the bit
+(path 1, one launch) against the batch without it (path 2, merged strips) and against single calls with it, alternating.
 
 tools/window_bench.py --ranged FILE [x0,y0,w,h] -- a window of a file on disk read in pieces (qb3x_open_ranged over os.pread,
 qb3x_read_windows_ranged) against qb3x_read_window of the same file read whole: wall-clock milliseconds (the reads are part of the
@@ -29,7 +35,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-CASES = {"headline": (16384, 16384, 3, 0, "NOISY3", 8), "config3": (8192, 8192, 8, 2, "LANDSAT16", 8), "u16x1": (8192, 8192, 1, 2, "LANDSAT16", 8)}
+CASES = {"headline": (16384, 16384, 3, 0, "NOISY3", 8), "config3": (8192, 8192, 8, 2, "LANDSAT16", 8), "u16x1": (8192, 8192, 1, 2, "LANDSAT16", 8),
+         "best": (16384, 16384, 3, 0, "NOISY3", 7)}
+SEEDS = {"best": 2}         # (bench.py's raster; the others: 3)
 
 
 def timed(fn, n):
@@ -45,17 +53,18 @@ def timed(fn, n):
     return a.elapsed_time(b) / n
 
 
-def run(case, kernels16=False):
+def run(case, kernels16=False, kernels_cf=False):
     import torch
-    from qb3_amd import synth, device as qdev, TYPESIZE, QB3X_WINK_U16
+    from qb3_amd import synth, device as qdev, TYPESIZE, QB3X_WINK_U16, QB3X_WINK_CF8
     w, h, b, dt, gen, mode = CASES[case]
     tsz = TYPESIZE[dt]
-    img = synth.generate(w, h, b, dt, gen, 3)
+    img = synth.generate(w, h, b, dt, gen, SEEDS.get(case, 3))
     raw = img.reshape(-1).view(torch.uint8)
     enc = qdev.DeviceEncoder(w, h, b, dt, mode=mode, want_index=False, index_chunk=2)
     dst, n, _ = enc.encode(raw)
     dec = qdev.DeviceDecoder(dst, n)
-    dec.set_window_kernels(QB3X_WINK_U16 if kernels16 else 0)
+    mask = (QB3X_WINK_U16 if kernels16 else 0) | (QB3X_WINK_CF8 if kernels_cf else 0)
+    dec.set_window_kernels(mask)
     full = torch.empty(raw.numel(), dtype=torch.uint8, device="cuda")
     rows = full.view(h, w * b * tsz)
     x0, y0 = 1001, 517
@@ -76,35 +85,49 @@ def run(case, kernels16=False):
         path, segs = dec.last_window
         assert torch.equal(crop, raw.view(h, -1)[wy:wy + hh, wx * b * tsz:(wx + ww) * b * tsz]), "window bytes"
         reps = 200 if side and side <= 1024 else 30
-        t_win, t_old = [], []
+        t_win, t_off, t_old = [], [], []
+        off = {}
         for _ in range(3):                              # alternating, three rounds each
             t_win.append(timed(window, reps))
+            if kernels_cf:                              # the same call without the bit
+                dec.set_window_kernels(mask & ~QB3X_WINK_CF8)
+                t_off.append(timed(window, reps))
+                off = {"path_off": dec.last_window[0], "segments_off": dec.last_window[1], "window_off_ms": [round(t, 4) for t in t_off]}
+                assert torch.equal(crop, raw.view(h, -1)[wy:wy + hh, wx * b * tsz:(wx + ww) * b * tsz]), "window bytes without the bit"
+                dec.set_window_kernels(mask)
             t_old.append(timed(decode_and_crop, reps))
         qdev.profile_reset()
         qdev.profile_enable(1)
         for _ in range(20):
             window()
+        for _ in range(5 if kernels_cf else 0):         # dec_units: the whole decode's kernel on the same container in the same run
+            dec.decode(dst, out=full)
         torch.cuda.synchronize()
         qdev.profile_enable(0)
         prof = qdev.profile_report()
-        kern = {k: round(v[0] / v[1], 4) for k, v in prof.items() if k in ("dec_window", "dec_window16", "dec_units")}
-        print(json.dumps({"case": case, "kernels16": kernels16, "window": [wx, wy, ww, hh], "path": path, "segments": segs, "window_ms": [round(t, 4) for t in t_win],
-                          "decode_and_crop_ms": [round(t, 4) for t in t_old], "kernel_ms": kern}), flush=True)
+        kern = {k: round(v[0] / v[1], 4) for k, v in prof.items() if k in ("dec_window", "dec_window16", "dec_window_best", "dec_units")}
+        line = {"case": case, "kernels16": kernels16, "kernels_cf": kernels_cf, "window": [wx, wy, ww, hh], "path": path, "segments": segs,
+                "window_ms": [round(t, 4) for t in t_win]}
+        line.update(off)
+        line.update({"decode_and_crop_ms": [round(t, 4) for t in t_old], "kernel_ms": kern})
+        print(json.dumps(line), flush=True)
 
 
 BATCH_CASES = {"batch256": (16384, 16384, 3, 2, 64, 256), "batch1024": (16384, 16384, 3, 2, 64, 1024), "batch_path3": (4096, 4096, 3, 0, 16, 256)}
+BATCH_CASES_CF = {"best256": (16384, 16384, 3, 2, 64, 256), "best1024": (16384, 16384, 3, 2, 64, 1024)}      # --kernels-cf: QB3M_BEST, bench.py's raster
 
 
-def run_batch(case):
+def run_batch(case, kernels_cf=False):
     import numpy as np
     import torch
-    from qb3_amd import synth, device as qdev
-    w, h, b, level, count, side = BATCH_CASES[case]
-    img = synth.generate(w, h, b, 0, "NOISY3", 3)
+    from qb3_amd import synth, device as qdev, QB3X_WINK_CF8
+    w, h, b, level, count, side = (BATCH_CASES_CF if kernels_cf else BATCH_CASES)[case]
+    img = synth.generate(w, h, b, 0, "NOISY3", 2 if kernels_cf else 3)
     raw = img.reshape(-1).view(torch.uint8)
-    enc = qdev.DeviceEncoder(w, h, b, 0, mode=8, want_index=False, index_chunk=level)
+    enc = qdev.DeviceEncoder(w, h, b, 0, mode=7 if kernels_cf else 8, want_index=False, index_chunk=level)
     dst, n, _ = enc.encode(raw)
     dec = qdev.DeviceDecoder(dst, n)
+    dec.set_window_kernels(QB3X_WINK_CF8 if kernels_cf else 0)
     rng = np.random.default_rng(64 + side)
     rects = []
     while len(rects) < count:
@@ -131,9 +154,15 @@ def run_batch(case):
     paths = dec.last_windows
     segs = dec.last_window[1]
     reps = 50 if level else 10
-    t_batch, t_single = [], []
+    t_batch, t_off, t_single = [], [], []
+    off = {}
     for _ in range(3):                                  # alternating, three rounds each
         t_batch.append(timed(batch, reps))
+        if kernels_cf:                                  # the same batch without the bit
+            dec.set_window_kernels(0)
+            t_off.append(timed(batch, reps))
+            off = {"paths_off": sorted(set(dec.last_windows)), "segments_off": dec.last_window[1], "batch_off_ms": [round(t, 4) for t in t_off]}
+            dec.set_window_kernels(QB3X_WINK_CF8)
         t_single.append(timed(singles, reps))
     qdev.profile_reset()
     qdev.profile_enable(1)
@@ -142,11 +171,13 @@ def run_batch(case):
     torch.cuda.synchronize()
     qdev.profile_enable(0)
     prof = qdev.profile_report()
-    kern = {k: round(v[0] / v[1], 4) for k, v in prof.items() if k in ("dec_window", "dec_units")}
-    launches = {k: v[1] / 20 for k, v in prof.items() if k == "dec_window"}
-    print(json.dumps({"case": case, "windows": count, "side": side, "paths": sorted(set(paths)), "segments": segs,
-                      "batch_ms": [round(t, 4) for t in t_batch], "single_calls_ms": [round(t, 4) for t in t_single],
-                      "ratio": round(min(t_batch) / min(t_single), 4), "kernel_ms": kern, "launches_per_call": launches}), flush=True)
+    kern = {k: round(v[0] / v[1], 4) for k, v in prof.items() if k in ("dec_window", "dec_window_best", "dec_units")}
+    launches = {k: v[1] / 20 for k, v in prof.items() if k in ("dec_window", "dec_window_best")}
+    line = {"case": case, "windows": count, "side": side, "paths": sorted(set(paths)), "segments": segs, "batch_ms": [round(t, 4) for t in t_batch]}
+    line.update(off)
+    line.update({"single_calls_ms": [round(t, 4) for t in t_single], "ratio": round(min(t_batch) / min(t_single), 4), "kernel_ms": kern,
+                 "launches_per_call": launches})
+    print(json.dumps(line), flush=True)
 
 
 def write_case(case, path):
@@ -214,8 +245,8 @@ def run_ranged(path, rect=None, kernels16=False):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
-    k16 = "--kernels16" in args
-    args = [a for a in args if a != "--kernels16"]
+    k16, kcf = "--kernels16" in args, "--kernels-cf" in args
+    args = [a for a in args if a not in ("--kernels16", "--kernels-cf")]
     if args and args[0] == "--ranged":
         if len(args) < 2:
             sys.exit("window_bench: --ranged takes a file (and, optionally, x0,y0,w,h)")
@@ -226,16 +257,17 @@ if __name__ == "__main__":
         write_case(args[1], args[2])
     elif args and args[0] == "--batch":
         if len(args) > 1:
-            run_batch(args[1])
+            run_batch(args[1], kcf)
         else:
-            for case in BATCH_CASES:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--batch", case], timeout=300)
+            for case in (BATCH_CASES_CF if kcf else BATCH_CASES):
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--batch", case] + (["--kernels-cf"] if kcf else []), timeout=300)
                 if r.returncode:
                     sys.exit("window_bench: %s ended with status %d; nothing more is run" % (case, r.returncode))
     elif args:
-        run(args[0], k16)
+        run(args[0], k16, kcf)
     else:
-        for case in ("headline", "config3"):
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), case] + (["--kernels16"] if k16 else []), timeout=420)
+        for case in ("headline", "config3") + (("best",) if kcf else ()):
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), case] + (["--kernels16"] if k16 else []) + (["--kernels-cf"] if kcf and case == "best" else []),
+                               timeout=420)
             if r.returncode:
                 sys.exit("window_bench: %s ended with status %d; nothing more is run" % (case, r.returncode))
