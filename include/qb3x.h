@@ -110,14 +110,16 @@ size_t qb3x_last_window_segments(const decsp p);
 /* Rasters beyond path 1's own that take a window kernel, per decoder handle; default 0: every window call goes as described above.
  * Honoured by qb3x_decode_window_device, qb3x_decode_windows_device, qb3x_read_window and qb3x_read_windows, and on a handle of
  * qb3x_open_ranged by qb3x_read_windows_ranged, qb3x_decode_windows_ranged and qb3x_ranged_table_ranges: with QB3X_WINK_U16 these
- * read a 16-bit raster the kernels take in pieces (below), without it whole.  Unknown bits are ignored; a NULL handle: no-op.  The
- * bytes written are the same with and without a bit: the bit only chooses the way.  Harmless on a handle whose raster the kernels of
- * the bits set do not take (other value sizes, other band counts, other modes, a container whose RLE0 pass won, STORED containers,
- * narrow images, a table without block fields, an out-of-band d_index).
- * QB3X_WINK_CF8 adds NO pieces shortcut on a handle of qb3x_open_ranged: such a file is still read whole, once a call, and its
- * windows then go through qb3x_decode_windows_device's way, which takes the kernel. */
+ * read a 16-bit raster the kernels take in pieces (below), without it whole, and with QB3X_WINK_CF8 an 8-bit common-factor raster
+ * the kernels take.  Unknown bits are ignored; a NULL handle: no-op.  The bytes written are the same with and without a bit: the bit
+ * only chooses the way.  Harmless on a handle whose raster the kernels of the bits set do not take (other value sizes, other band
+ * counts, other modes, a container whose RLE0 pass won, STORED containers, narrow images, a table without block fields, an
+ * out-of-band d_index): such a raster goes, and on a ranged handle is read, as it does with the mask at 0.
+ * On a handle of qb3x_open_ranged the pieces of a common-factor raster are decoded with nothing but the HOST's check of the table
+ * chunks in front of them: as on path 1, an entry's entering value or factor that was changed under a check sealed again is outside
+ * "damage costs time, never pixels" -- no kernel and no whole decode from the table can tell it, and all give the same wrong pixels. */
 #define QB3X_WINK_U16 1u   /* 16-bit rasters of 1, 2, 3, 4, 6, 8 bands, FTL / BASE, level-2 table: window kernel (path 1) instead of strips (path 2); ranged handles: pieces instead of the whole container */
-#define QB3X_WINK_CF8 2u   /* 8-bit rasters of 1, 3, 4 bands in the common-factor modes (QB3M_CF, QB3M_CF_H; QB3M_BEST / QB3M_CF_RLE where the RLE0 pass did not win), table with block fields: window kernel (path 1) instead of strips (path 2) */
+#define QB3X_WINK_CF8 2u   /* 8-bit rasters of 1, 3, 4 bands in the common-factor modes (QB3M_CF, QB3M_CF_H; QB3M_BEST / QB3M_CF_RLE where the RLE0 pass did not win), table of version 3 with block fields (level 1 or 2): window kernel (path 1) instead of strips (path 2); ranged handles: pieces instead of the whole container */
 void qb3x_set_decoder_window_kernels(decsp p, unsigned mask);
 
 /* A batch of windows: n rectangles of ONE raster in one call -- what a tile server, a viewer or a cropping loader asks of a raster
@@ -167,9 +169,12 @@ int    qb3x_window_path(const decsp p, size_t i);   /* 0 failed, 1 / 2 / 3 as qb
  * rows, one bad rectangle refuses the batch (QB3E_EINV) before rd is called.  A handle that is not qb3x_open_ranged's: QB3E_EINV.
  * The shortcut is taken where path 1 is -- 8-bit, 1 / 3 / 4 bands, FTL / BASE, a level-2 table of version 3; and, on a handle with
  * qb3x_set_decoder_window_kernels(p, QB3X_WINK_U16), 16-bit data (signed or unsigned) of 1, 2, 3, 4, 6 or 8 bands, FTL / BASE /
- * BASE_Z, a level-2 table of version 3, every device destination on an even address -- and what it reads is fixed by these rules,
- * with B blocks a segment, B as qb3x_window_segments reports (64; 32 for eight 16-bit bands, 21 for six), so that qb3x_ranged_bytes
- * is a number the caller can compute beforehand:
+ * BASE_Z, a level-2 table of version 3, every device destination on an even address; and, on a handle with QB3X_WINK_CF8, 8-bit
+ * data of 1 / 3 / 4 bands in the common-factor modes (QB3M_CF, QB3M_CF_H; QB3M_BEST / QB3M_CF_RLE where the RLE0 pass did not win:
+ * the header's mode byte says which), a table of version 3 and level 1 or 2 with a field per block (E = 6 + 3 * bands + 192; its
+ * chunk heads say flags 3), any destination address -- and what it reads is fixed by these rules, with B blocks a segment, B as
+ * qb3x_window_segments reports (64; 32 for eight 16-bit bands, 21 for six), so that qb3x_ranged_bytes is a number the caller can
+ * compute beforehand:
  *   table chunks   With S0 / S1 the first / last index segment that holds a block of window i (qb3x_window_segments' rule), K the
  *                  table's entries and N its entries per chunk: the chunks S0 / N .. min(S1 + 1, K - 1) / N of every window, and
  *                  always the table's last chunk (K - 1) / N; each once.  Chunk c is the container's bytes from T + c * (16 + N * E),
@@ -185,7 +190,8 @@ int    qb3x_window_path(const decsp p, size_t i);   /* 0 failed, 1 / 2 / 3 as qb
  *                  lie at most `gap` bytes apart (qb3x_set_ranged_gap; 0 by default); every merged range is one call of rd.
  * qb3x_ranged_bytes / qb3x_ranged_reads: the bytes and the calls the handle's last ranged call asked of rd.
  * The pieces go up packed back to back, with the entries their segments use and a sorted piece list, and ONE launch decodes every
- * window from them (profile name dec_window_ranged; dec_window16_ranged for 16-bit rasters); the kernel reads no word outside a
+ * window from them (profile name dec_window_ranged; dec_window16_ranged for 16-bit rasters, dec_window_best_ranged for 8-bit
+ * common-factor ones); the kernel reads no word outside a
  * segment's piece and no byte outside the entries that went up, whatever the entries say.
  * Falling back costs time and bytes, never pixels: a chunk or the table's end failing its check, pieces whose window ends with a
  * nonzero status, a raster the shortcut does not take, a container without a usable table -- the call reads the WHOLE container
@@ -340,7 +346,7 @@ size_t qb3_decode(decsp p, void *destination);                                  
  * events on the launch stream; totals are resolved at the library's own synchronisation points.
  * Kernel names: enc_units, enc_scan, enc_concat, enc_seams, enc_best_units, enc_best_scan, enc_best_recode,
  * dec_index_table, dec_index_serial, dec_index_prev, dec_index_scan, dec_units, dec_segments, dec_window (the window kernel of
- * qb3x_decode_window_device, path 1), dec_window16 (the 16-bit window kernels: path 1 under QB3X_WINK_U16), dec_window_best (the window kernels of the 8-bit common-factor modes: path 1 under QB3X_WINK_CF8), dec_window_ranged (the same from fetched pieces: the ranged calls), dec_window16_ranged (... of 16-bit rasters under QB3X_WINK_U16), reindex_fill, reindex_finish (qb3x_reindex_device: the table's entries; everything else of the
+ * qb3x_decode_window_device, path 1), dec_window16 (the 16-bit window kernels: path 1 under QB3X_WINK_U16), dec_window_best (the window kernels of the 8-bit common-factor modes: path 1 under QB3X_WINK_CF8), dec_window_ranged (the same from fetched pieces: the ranged calls), dec_window16_ranged (... of 16-bit rasters under QB3X_WINK_U16), dec_window_best_ranged (... of 8-bit common-factor rasters under QB3X_WINK_CF8), reindex_fill, reindex_finish (qb3x_reindex_device: the table's entries; everything else of the
  * new container).
  * level: 0 off, 1 every kernel, 2 all but the microsecond kernels (enc_scan, enc_seams, enc_best_scan), whose two
  * events cost more than they take. */

@@ -323,8 +323,8 @@ class RangedReader:
 
     def set_window_kernels(self, mask):
         """qb3x_set_decoder_window_kernels on the ranged handle: QB3X_WINK_U16 -- 16-bit rasters of 1, 2, 3, 4, 6, 8 bands with a
-        level-2 table are read in pieces too (else they are read whole, every call); QB3X_WINK_CF8 -- 8-bit common-factor rasters are
-        still read whole, their windows then take the window kernel; 0 (the default): none"""
+        level-2 table are read in pieces too (else they are read whole, every call); QB3X_WINK_CF8 -- so are 8-bit rasters of 1, 3, 4
+        bands in the common-factor modes whose table carries block fields; 0 (the default): none"""
         lib.qb3x_set_decoder_window_kernels(self.p, int(mask))
 
     def set_gap(self, nbytes):

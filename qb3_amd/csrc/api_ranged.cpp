@@ -1,8 +1,9 @@
 // qb3_amd/csrc/api_ranged.cpp -- ranged window reads (include/qb3x.h: qb3x_open_ranged, qb3x_read_windows_ranged,
 // qb3x_decode_windows_ranged): windows of a container that is read through a function of the caller's, fetching only the table chunks
 // and the pieces of the stream that hold the rectangles.  The rules of what is read are stated in qb3x.h; the kernels that decode from
-// the pieces are k_dec_wins_ranged.hip (8-bit rasters) and k_dec_wins16_ranged.hip (16-bit ones, on a handle that asked: QB3X_WINK_U16);
-// everything the shortcut does not take goes, with the whole container, the way of api_window.cpp.
+// the pieces are k_dec_wins_ranged.hip (8-bit rasters), k_dec_wins16_ranged.hip (16-bit ones, on a handle that asked: QB3X_WINK_U16) and
+// k_dec_wins_best_ranged.hip (8-bit rasters in the common-factor modes, on a handle that asked: QB3X_WINK_CF8); everything the shortcut
+// does not take goes, with the whole container, the way of api_window.cpp.
 #include <new>
 #include "qb3_host.h"
 
@@ -35,14 +36,15 @@ struct Chunks {
 };
 
 // does the shortcut take this handle's raster and table, and with which kernels (pure: no device, no reader)
-enum class Shortcut { none, u8, u16 };
+enum class Shortcut { none, u8, u16, cf8 };
 Shortcut ranged_shortcut(const decs *p, Geometry &g, DecPlan &plan, IxTable &ixt, Chunks &ch) {
     if (p->mode == QB3M_STORED || p->xsize < 4 || p->ysize < 4 || !p->ix_K || !p->ix_bl || p->ix_ver < 3 || !p->ix_pads || is_rle_mode(p->mode)) return Shortcut::none;
     g = decoder_geometry(p, p->xsize, p->ysize, 0);
     plan = plan_decode(g);
     ixt = handle_table(p, (const uint8_t *)p);          // (the table is not in device memory: the base only has to be non-null)
     const Shortcut family = decode_window_ok(g, plan, ixt) ? Shortcut::u8
-                          : (p->win_kernels & QB3X_WINK_U16) && decode_window16_ok(g, plan, ixt) ? Shortcut::u16 : Shortcut::none;
+                          : (p->win_kernels & QB3X_WINK_U16) && decode_window16_ok(g, plan, ixt) ? Shortcut::u16
+                          : (p->win_kernels & QB3X_WINK_CF8) && decode_window_best_ok(g, plan, ixt) ? Shortcut::cf8 : Shortcut::none;
     if (family == Shortcut::none) return family;
     ch.off = p->ix_off; ch.K = p->ix_K; ch.N = p->ix_per_chunk; ch.E = p->ix_E; ch.count = (uint32_t)ix_chunks(ixt);
     return ch.at(ch.count - 1) + ch.size(ch.count - 1) <= p->rg_size ? family : Shortcut::none;
@@ -66,11 +68,12 @@ void chunk_list(const Geometry &g, const Chunks &ch, const qb3x_window *wins, si
     chunks.erase(std::unique(chunks.begin(), chunks.end()), chunks.end());
 }
 
-// The host twin of ix_check_chunk (qb3_kernels.h): head, pad, the mark behind the last chunk, and the 16-bit check of the entries
-bool chunk_sound(const decs *p, const Chunks &ch, uint32_t c, const uint8_t *b) {
+// The host twin of ix_check_chunk (qb3_kernels.h): head (flag bit 0: common-factor entries; bit 1: block fields, which the shortcut
+// requires), pad, the mark behind the last chunk, and the 16-bit check of the entries
+bool chunk_sound(const decs *p, const Chunks &ch, uint32_t c, const uint8_t *b, uint32_t flags) {
     const uint32_t n = ch.entries(c) * ch.E, len = IX_HEAD + n;
     const uint32_t blocks = b[8] | (b[9] << 8) | (b[10] << 16) | ((uint32_t)b[11] << 24);
-    if (b[0] != 'i' || b[1] != 'x' || (uint32_t)(b[2] | (b[3] << 8)) != len || b[4] != p->ix_ver || (b[5] & 3) != 2u || blocks != p->ix_blocks) return false;
+    if (b[0] != 'i' || b[1] != 'x' || (uint32_t)(b[2] | (b[3] << 8)) != len || b[4] != p->ix_ver || (b[5] & 3) != flags || blocks != p->ix_blocks) return false;
     if (b[len] != 'z' || b[len + 1] != 'z' || b[len + 2] != 4 || b[len + 3] != 0) return false;
     if (c + 1 == ch.count && (b[len + IX_PAD] != 'D' || b[len + IX_PAD + 1] != 'T')) return false;
     uint32_t s = 0;
@@ -81,7 +84,7 @@ bool chunk_sound(const decs *p, const Chunks &ch, uint32_t c, const uint8_t *b) 
 
 // Stage 1: the chunks of the list, from the handle's cache or the reader (each whole, verified before it is kept).  data[i]: chunk
 // chunks[i].  0: all sound; 1: a chunk failed its check; 2: the reader failed
-int fetch_chunks(decs *p, const Chunks &ch, const std::vector<uint32_t> &chunks, std::vector<const uint8_t *> &data) {
+int fetch_chunks(decs *p, const Chunks &ch, const std::vector<uint32_t> &chunks, std::vector<const uint8_t *> &data, uint32_t flags) {
     data.assign(chunks.size(), nullptr);
     for (size_t i = 0; i < chunks.size(); i++) {
         bool cached = false;
@@ -89,7 +92,7 @@ int fetch_chunks(decs *p, const Chunks &ch, const std::vector<uint32_t> &chunks,
         if (cached) continue;
         std::vector<uint8_t> b(ch.size(chunks[i]));
         if (!rg_read(p, ch.at(chunks[i]), b.data(), b.size())) return 2;
-        if (!chunk_sound(p, ch, chunks[i], b.data())) return 1;
+        if (!chunk_sound(p, ch, chunks[i], b.data(), flags)) return 1;
         p->rg_cache_bytes += b.size();
         p->rg_chunks.emplace_back(chunks[i], std::move(b));
     }
@@ -106,6 +109,10 @@ void trim_cache(decs *p) {
 
 struct Piece { uint32_t seg0, nseg, ent0, word0, sw0_lo, sw0_hi, nwords, pad_; };      // WinPiece of qb3_win.h, as uploaded
 static_assert(sizeof(Piece) == WIN_PIECE_BYTES, "the piece list is uploaded as it is");
+// the kernels the shortcut goes through, by their launchers
+int (*const ranged_launchers[])(const Geometry &, const DecPlan &, uint32_t, uint64_t, const void *, const void *, size_t, const void *, size_t, const void *,
+                                const uint32_t *, uint32_t *, void *, const IxTable &) = {      // in Shortcut's order
+    nullptr, launch_decode_windows_ranged, launch_decode_windows16_ranged, launch_decode_windows_best_ranged };
 
 // The whole container through the reader, once, and the windows the way of qb3x_read_windows / qb3x_decode_windows_device
 size_t whole_container(decsp p, const qb3x_window *wins, size_t n, uint8_t *paths, bool host, hipStream_t st) {
@@ -157,10 +164,11 @@ size_t stored_windows(decsp p, const qb3x_window *wins, size_t n, uint8_t *paths
 }
 
 // The shortcut.  Marks the windows it gave their pixels (paths[i] = 1) and counts their segments.  1: went through (fall back for the
-// windows that are left); 0: the table is not to be trusted, nothing was written; -1: the call failed (p->error is set).  wide: a
-// 16-bit raster (Shortcut::u16) -- its own blocks per segment (g.seg_blocks), its value size, its kernels; all else is one code
+// windows that are left); 0: the table is not to be trusted, nothing was written; -1: the call failed (p->error is set).  family:
+// whose kernels -- a 16-bit raster (Shortcut::u16) has its own blocks per segment (g.seg_blocks) and value size, a common-factor one
+// (Shortcut::cf8) its own entries (ch.E) and head flags; all else is one code
 int pieces_windows(decsp p, const Geometry &g, const DecPlan &plan, const IxTable &ixt, const Chunks &ch, const qb3x_window *wins, size_t n,
-                   uint8_t *paths, size_t *segs, bool host, hipStream_t st, bool wide) {
+                   uint8_t *paths, size_t *segs, bool host, hipStream_t st, Shortcut family) {
     const size_t tsz = szof(p->type), pix = p->nbands * tsz;
     const uint64_t csize = p->rg_size, off = (uint64_t)(p->s_in - p->s_start), base = off & ~(uint64_t)3, in_bits = (uint64_t)p->s_size * 8;
     const uint32_t in_bit0 = (uint32_t)(8 * (off & 3));
@@ -168,7 +176,7 @@ int pieces_windows(decsp p, const Geometry &g, const DecPlan &plan, const IxTabl
     std::vector<uint32_t> chunks;
     std::vector<const uint8_t *> cdata;
     chunk_list(g, ch, wins, n, chunks);
-    const int got = fetch_chunks(p, ch, chunks, cdata);
+    const int got = fetch_chunks(p, ch, chunks, cdata, family == Shortcut::cf8 ? 3u : 2u);
     if (got == 2) { p->error = QB3E_ERR; return -1; }
     if (got) return 0;
     auto entry = [&](uint32_t k) -> const uint8_t * {
@@ -191,7 +199,7 @@ int pieces_windows(decsp p, const Geometry &g, const DecPlan &plan, const IxTabl
     }
     runs.resize(m + 1);
     // a piece per run whose two ends make sense: inside the stream, no longer than its segments can be (px_cap_dw: the worst-case
-    // segment of either family; a table that says otherwise is not this stream's; the waves of such a run find no piece and raise
+    // segment of every family; a table that says otherwise is not this stream's; the waves of such a run find no piece and raise
     // their window's status)
     struct Span { uint64_t a, b; size_t at; };         // container bytes [a, b); at: where they start in the packed words (bytes)
     std::vector<Piece> pieces;
@@ -273,7 +281,7 @@ int pieces_windows(decsp p, const Geometry &g, const DecPlan &plan, const IxTabl
     hipError_t e = hipMemcpyAsync(p->d_rg.p, up, upbytes - 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_status, 0, stbytes, st);
     if (e != hipSuccess) return hip_fail("ranged windows: upload", e);
-    if ((wide ? launch_decode_windows16_ranged : launch_decode_windows_ranged)(g, plan, in_bit0, in_bits, up, d_up, n, d_up + dbytes, pieces.size(), d_up + dbytes + pbytes,
+    if (ranged_launchers[(int)family](g, plan, in_bit0, in_bits, up, d_up, n, d_up + dbytes, pieces.size(), d_up + dbytes + pbytes,
                                      (const uint32_t *)(d_up + dbytes + pbytes + ebytes), d_status, st, ixt)) return hip_fail("ranged windows: launch", hipSuccess);
     e = hipMemcpyAsync(p->h_wst.p, d_status, stbytes, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = wait_stream(st);
@@ -315,7 +323,7 @@ size_t ranged_call(decsp p, const qb3x_window *wins, size_t n, bool host, hipStr
     // applies the same test (host destinations are decoded into the handle's buffer, every window on a dword)
     for (size_t i = 0; family == Shortcut::u16 && !host && i < n; i++) if ((uintptr_t)wins[i].dst & 1) family = Shortcut::none;
     if (family != Shortcut::none) {
-        const int went = pieces_windows(p, g, plan, ixt, ch, wins, n, paths, &segs, host, st, family == Shortcut::u16);
+        const int went = pieces_windows(p, g, plan, ixt, ch, wins, n, paths, &segs, host, st, family);
         trim_cache(p);
         if (went < 0) return 0;
     }

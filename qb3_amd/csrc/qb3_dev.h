@@ -318,6 +318,11 @@ int launch_decode_windows_ranged(const Geometry &g, const DecPlan &plan, uint32_
 int launch_decode_windows16_ranged(const Geometry &g, const DecPlan &plan, uint32_t in_bit0, uint64_t in_bits, const void *h_descs, const void *d_descs,
                                    size_t n, const void *d_pieces, size_t npieces, const void *d_entries, const uint32_t *d_words,
                                    uint32_t *d_status, void *stream, const IxTable &ix);
+// ... and of an 8-bit common-factor raster the window kernels of k_dec_win_best.hip take (k_dec_wins_best_ranged.hip;
+// decode_window_best_ok): the same arguments, entries with block fields, destinations on any address
+int launch_decode_windows_best_ranged(const Geometry &g, const DecPlan &plan, uint32_t in_bit0, uint64_t in_bits, const void *h_descs, const void *d_descs,
+                                      size_t n, const void *d_pieces, size_t npieces, const void *d_entries, const uint32_t *d_words,
+                                      uint32_t *d_status, void *stream, const IxTable &ix);
 
 // Reindex (k_reindex.hip): the table chunks this library's encoder writes for a raster, made from the index a plain walk of its stream
 // has rebuilt (launch_decode with index == nullptr leaves it in ws behind the status words), and the new container around them.

@@ -1,14 +1,14 @@
 // tools/qb3window.cpp -- a rectangle of a QB3 file as a PNM image, reading only the bytes of the file that hold it: the command line
 // caller of qb3x_open_ranged / qb3x_read_windows_ranged (include/qb3x.h), with pread as the reader.  A file with a level-2 restart
-// table (cqb3x with QB3X_INDEX_CHUNK=2, qb3index -2) is read in pieces -- an 8-bit one always, a 16-bit one with -k; any other file
-// is read whole and gives the same pixels.
+// table (cqb3x with QB3X_INDEX_CHUNK=2, qb3index -2) is read in pieces -- an 8-bit FTL / BASE one always, a 16-bit one with -k, an
+// 8-bit common-factor one with -K; any other file is read whole and gives the same pixels.
 //
 //   qb3window [-v] [-k] [-K] [-g gap] in.qb3 x0,y0,w,h out.pnm
 //
 //   -g gap  merge two byte ranges that lie at most `gap` bytes apart (fewer reads, more bytes; default 0)
 //   -k      16-bit files too are read in pieces (qb3x_set_decoder_window_kernels, QB3X_WINK_U16)
-//   -K      8-bit files of 1, 3, 4 bands in the common-factor modes (cqb3x -b) are still read whole, but the window is then decoded by the
-//           window kernel, not from strips of block rows (QB3X_WINK_CF8)
+//   -K      8-bit files of 1, 3, 4 bands in the common-factor modes (cqb3x -b, qb3tiles -b) too are read in pieces (QB3X_WINK_CF8);
+//           without it such a file is read whole
 //   -v      prints bytes read and calls of the reader against the file's size
 #include "qb3x.h"
 #include <cstdint>
@@ -22,7 +22,8 @@
 
 namespace {
 
-const char *USAGE = "qb3window [-v] [-k] [-K] [-g gap] in.qb3 x0,y0,w,h out.pnm\n";
+const char *USAGE = "qb3window [-v] [-k] [-K] [-g gap] in.qb3 x0,y0,w,h out.pnm\n"
+                    "  -k  read 16-bit files in pieces too    -K  read 8-bit common-factor files (cqb3x -b) in pieces too\n";
 
 int fail(const std::string &msg) {
     fprintf(stderr, "qb3window: %s\n", msg.c_str());

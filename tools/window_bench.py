@@ -26,8 +26,12 @@ work) of a cold window (a fresh handle a call), a warm one (the table chunks cac
 a few, with the bytes read beside each.  The window defaults to 512 x 512 in the raster's middle.  One JSON line.
 --kernels16 sets QB3X_WINK_U16 on the ranged handles: a 16-bit file is then read in pieces too (without it: whole, every call), and
 the line also carries the kernel's own time (dec_window16_ranged, from the library's profile in a pass of its own).
+--kernels-cf sets QB3X_WINK_CF8 on them: an 8-bit common-factor file (--write best) is then read in pieces too.  The same calls on
+handles without the bit -- the file read whole, every call -- alternate with them in the same process, round by round (cold_off_ms,
+warm_off_ms and their bytes and reads beside cold_ms, warm_ms), and the kernel's own time is dec_window_best_ranged's.
 
-tools/window_bench.py --write CASE FILE -- writes CASE's container (level-2 table) to FILE, for --ranged to read."""
+tools/window_bench.py --write CASE FILE -- writes CASE's container (level-2 table) to FILE, for --ranged to read; CASE best is the
+container of bench.py's second configuration (16384 x 16384 x 3, QB3M_BEST)."""
 import json
 import os
 import subprocess
@@ -184,18 +188,18 @@ def write_case(case, path):
     import torch
     from qb3_amd import synth, device as qdev
     w, h, b, dt, gen, mode = CASES[case]
-    img = synth.generate(w, h, b, dt, gen, 3)
+    img = synth.generate(w, h, b, dt, gen, SEEDS.get(case, 3))
     enc = qdev.DeviceEncoder(w, h, b, dt, mode=mode, want_index=False, index_chunk=2)
     dst, n, _ = enc.encode(img.reshape(-1).view(torch.uint8))
     dst[:n].cpu().numpy().tofile(path)
     print(json.dumps({"case": case, "file": os.path.basename(path), "file_bytes": n}), flush=True)
 
 
-def run_ranged(path, rect=None, kernels16=False):
+def run_ranged(path, rect=None, kernels16=False, kernels_cf=False):
     import time
     import numpy as np
     import qb3_amd
-    mask = qb3_amd.QB3X_WINK_U16 if kernels16 else 0
+    mask = (qb3_amd.QB3X_WINK_U16 if kernels16 else 0) | (qb3_amd.QB3X_WINK_CF8 if kernels_cf else 0)
     size = os.path.getsize(path)
     with qb3_amd.open_ranged(path) as rd:
         W, H = rd.width, rd.height
@@ -203,17 +207,23 @@ def run_ranged(path, rect=None, kernels16=False):
         w, h = min(512, W), min(512, H)
         rect = ((W - w) // 2, (H - h) // 2, w, h)
 
-    def wall(fn, n=5):
-        best, out = None, None
+    def wall(fn, n=5, other=None):
+        """the best of n calls of fn and its last result; other: a second function called after each, timed the same way"""
+        best, out, best2, out2 = None, None, None, None
         for _ in range(n):
             t0 = time.perf_counter()
             out = fn()
             t = (time.perf_counter() - t0) * 1e3
             best = t if best is None or t < best else best
-        return best, out
+            if other:
+                t0 = time.perf_counter()
+                out2 = other()
+                t = (time.perf_counter() - t0) * 1e3
+                best2 = t if best2 is None or t < best2 else best2
+        return (best, out, best2, out2) if other else (best, out)
 
-    def cold():
-        with qb3_amd.open_ranged(path, window_kernels=mask) as rd:
+    def cold(m=mask):
+        with qb3_amd.open_ranged(path, window_kernels=m) as rd:
             return rd.read_windows([rect])[0], rd.last_bytes, rd.last_reads, rd.last_windows[0]
 
     def whole():
@@ -221,26 +231,41 @@ def run_ranged(path, rect=None, kernels16=False):
 
     whole()                                             # (the device and the library's buffers are up before anything is timed)
     t_whole, want = wall(whole)
-    t_cold, (got, cold_bytes, cold_reads, path1) = wall(cold)
+    off = {}
+    if kernels_cf:                                      # with the bit and without it, round by round
+        t_cold, (got, cold_bytes, cold_reads, path1), t_off, (got_off, off_bytes, off_reads, path_off) = wall(cold, other=lambda: cold(mask & ~qb3_amd.QB3X_WINK_CF8))
+        assert np.array_equal(got_off, want), "the window without the bit is not the window of the whole file"
+        off = {"path_off": path_off, "cold_off_ms": round(t_off, 3), "cold_off_bytes": off_bytes, "cold_off_reads": off_reads}
+    else:
+        t_cold, (got, cold_bytes, cold_reads, path1) = wall(cold)
     assert np.array_equal(got, want), "the ranged window is not the window of the whole file"
     kern = {}
     with qb3_amd.open_ranged(path, window_kernels=mask) as rd:
         rd.read_windows([rect])
-        t_warm, got = wall(lambda: rd.read_windows([rect])[0])
+        if kernels_cf:
+            with qb3_amd.open_ranged(path, window_kernels=mask & ~qb3_amd.QB3X_WINK_CF8) as rd_off:
+                rd_off.read_windows([rect])
+                t_warm, got, t_off, got_off = wall(lambda: rd.read_windows([rect])[0], other=lambda: rd_off.read_windows([rect])[0])
+                assert np.array_equal(got_off, want)
+                off.update({"warm_off_ms": round(t_off, 3), "warm_off_bytes": rd_off.last_bytes, "warm_off_reads": rd_off.last_reads})
+        else:
+            t_warm, got = wall(lambda: rd.read_windows([rect])[0])
         warm_bytes, warm_reads = rd.last_bytes, rd.last_reads
-        if kernels16:                                   # the kernel's own time, in a pass of its own
+        if kernels16 or kernels_cf:                     # the kernel's own time, in a pass of its own
             from qb3_amd import device as qdev
             qdev.profile_reset()
             qdev.profile_enable(1)
             for _ in range(20):
                 rd.read_windows([rect])
             qdev.profile_enable(0)
-            kern = {k: round(v[0] / v[1], 4) for k, v in qdev.profile_report().items() if k in ("dec_window16_ranged", "dec_window_ranged")}
+            kern = {k: round(v[0] / v[1], 4) for k, v in qdev.profile_report().items() if k in ("dec_window16_ranged", "dec_window_ranged", "dec_window_best_ranged")}
     assert np.array_equal(got, want)
-    print(json.dumps({"file": os.path.basename(path), "file_bytes": size, "raster": [W, H], "window": list(rect), "kernels16": kernels16, "path": path1,
-                      "cold_ms": round(t_cold, 3), "cold_bytes": cold_bytes, "cold_reads": cold_reads,
-                      "warm_ms": round(t_warm, 3), "warm_bytes": warm_bytes, "warm_reads": warm_reads,
-                      "whole_file_ms": round(t_whole, 3), "whole_file_bytes": size, "kernel_ms": kern}), flush=True)
+    line = {"file": os.path.basename(path), "file_bytes": size, "raster": [W, H], "window": list(rect), "kernels16": kernels16, "kernels_cf": kernels_cf,
+            "path": path1, "cold_ms": round(t_cold, 3), "cold_bytes": cold_bytes, "cold_reads": cold_reads,
+            "warm_ms": round(t_warm, 3), "warm_bytes": warm_bytes, "warm_reads": warm_reads}
+    line.update(off)
+    line.update({"whole_file_ms": round(t_whole, 3), "whole_file_bytes": size, "kernel_ms": kern})
+    print(json.dumps(line), flush=True)
 
 
 if __name__ == "__main__":
@@ -250,7 +275,7 @@ if __name__ == "__main__":
     if args and args[0] == "--ranged":
         if len(args) < 2:
             sys.exit("window_bench: --ranged takes a file (and, optionally, x0,y0,w,h)")
-        run_ranged(args[1], tuple(int(v) for v in args[2].split(",")) if len(args) > 2 else None, k16)
+        run_ranged(args[1], tuple(int(v) for v in args[2].split(",")) if len(args) > 2 else None, k16, kcf)
     elif args and args[0] == "--write":
         if len(args) != 3 or args[1] not in CASES:
             sys.exit("window_bench: --write takes a case (%s) and a file" % ", ".join(CASES))
