@@ -33,6 +33,7 @@ QB3M_DEFAULT, QB3M_BASE, QB3M_BEST, QB3M_STORED, QB3M_INVALID = 8, 4, 7, 255, -1
 QB3X_REF_CBAND0 = 1
 QB3X_WINK_U16 = 1           # qb3x_set_decoder_window_kernels: the 16-bit window kernels
 QB3X_WINK_CF8 = 2           # ... the window kernels of the 8-bit common-factor modes (1, 3, 4 bands)
+QB3X_WINK_UNIT = 4          # ... the window kernels of the lane-per-unit rasters and of one-band 32/64-bit rasters (FTL / BASE)
 TYPESIZE = (1, 1, 2, 2, 4, 4, 8, 8)
 
 _vp, _sz, _u64 = C.c_void_p, C.c_size_t, C.c_uint64
@@ -324,7 +325,8 @@ class RangedReader:
     def set_window_kernels(self, mask):
         """qb3x_set_decoder_window_kernels on the ranged handle: QB3X_WINK_U16 -- 16-bit rasters of 1, 2, 3, 4, 6, 8 bands with a
         level-2 table are read in pieces too (else they are read whole, every call); QB3X_WINK_CF8 -- so are 8-bit rasters of 1, 3, 4
-        bands in the common-factor modes whose table carries block fields; 0 (the default): none"""
+        bands in the common-factor modes whose table carries block fields; QB3X_WINK_UNIT adds no ranged shortcut (the container is
+        read whole, once; its windows then take the window kernel from the uploaded copy); 0 (the default): none"""
         lib.qb3x_set_decoder_window_kernels(self.p, int(mask))
 
     def set_gap(self, nbytes):

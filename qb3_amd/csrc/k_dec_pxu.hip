@@ -13,36 +13,10 @@
 // Pixels: the lanes write their values into a tile in LDS laid out like the image ([row][block][x][band]; the tile takes the place of
 // the staged words, which are dead by then) and the wave stores the four rows of its blocks in pieces of up to sixteen bytes -- whole
 // runs of 4 x bands values a block, whatever the band count.
-#include "qb3_wide.h"
+#include "qb3_pxu.h"
 
 namespace qb3dev {
 
-template <typename T> __device__ __forceinline__ T pxu_shfl(T v, uint32_t src) {
-    if constexpr (sizeof(T) == 8) return (T)__shfl((unsigned long long)v, (int)src, 64);
-    else return (T)__shfl((unsigned)v, (int)src, 64);
-}
-// exclusive scan along the lanes `stride` apart (a band's units)
-template <typename T> __device__ __forceinline__ T pxu_exscan_band(T v, uint32_t stride) {
-    const uint32_t lane = threadIdx.x & 63;
-    T x = v;
-    for (uint32_t d = stride; d < 64; d <<= 1) {
-        T y;
-        if constexpr (sizeof(T) == 8) y = (T)__shfl_up((unsigned long long)x, d, 64);
-        else y = (T)__shfl_up((unsigned)x, d, 64);
-        if (lane >= d) x = (T)(x + y);
-    }
-    return (T)(x - v);
-}
-// the band map, four bits a band (a lane indexes it by its band: kernel arguments live in scalar registers)
-__device__ __forceinline__ uint64_t pxu_band_nibbles(const DecArgs &a0) {
-    uint64_t n = 0;
-    for (uint32_t c = 0; c < (uint32_t)MAXBANDS; c++) n |= (uint64_t)(a0.g.cband[c] & 15u) << (4 * c);
-    return n;
-}
-template <int N> struct PxuPiece;
-template <> struct PxuPiece<16> { typedef uint32_t v __attribute__((ext_vector_type(4))); };
-template <> struct PxuPiece<8> { typedef uint32_t v __attribute__((ext_vector_type(2))); };
-template <> struct PxuPiece<4> { typedef uint32_t v; };
 template <int N, typename T>
 __device__ __forceinline__ void pxu_store_rows(uint8_t *img, const uint8_t *tile, const uint64_t *origin, uint64_t stride, uint32_t n, uint32_t ppb, uint32_t row_bytes, uint32_t row_pitch_bytes) {
     typedef typename PxuPiece<N>::v V;
@@ -70,17 +44,7 @@ __device__ __forceinline__ void pxu_pixels(const DecArgs &a, uint8_t *tile8, uin
         const uint32_t y0 = (4 * by + 4 > a.g.h) ? a.g.h - 4 : 4 * by;
         origin[lane] = (uint64_t)y0 * stride + (uint64_t)x0 * B;
     }
-    if (act) {
-        const uint32_t e0 = blk * 4 * B + c;
-#pragma unroll
-        for (uint32_t i = 0; i < 16; i++) {
-            const uint32_t nib = curve_nib(order, i);
-            tile[e0 + (nib >> 2) * RP + (nib & 3) * B] = o[i];
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    pxu_tile_fill<T>(tile, o, act, blk, c, B, RP, order);
     const uint32_t RB = 4 * B * (uint32_t)sizeof(T);        // bytes of a block's row: a multiple of 4
     uint8_t *img = (uint8_t *)a.img;
     if ((RB & 15) == 0) pxu_store_rows<16, T>(img, tile8, origin, stride, nb_here * (RB >> 4), RB >> 4, RB, RP * (uint32_t)sizeof(T));
@@ -89,20 +53,6 @@ __device__ __forceinline__ void pxu_pixels(const DecArgs &a, uint8_t *tile8, uin
 }
 // the 8-bit rows of a raster whose rows are not dword aligned: value-aligned means byte-aligned there, which the vector stores take
 // as they are (the hardware's unaligned access mode); nothing to do.
-
-// bytes of LDS a wave needs: the staged words and, in their place afterwards, the tile; then a slot per block
-// (PXU_PAD zero words behind the staged ones: what wide_values_lds reads beyond a position inside the staged bits, qb3_wide.h)
-constexpr uint32_t PXU_PAD = WIDE_PAD_DW;
-__host__ __device__ inline uint32_t pxu_wave_bytes(uint32_t in_cap_dw, uint32_t tsz) {
-    const uint32_t st = 4 * (in_cap_dw + PXU_PAD), tl = 16 * 64 * tsz;
-    return (((st > tl ? st : tl) + 15u) & ~15u) + 8 * 32;
-}
-
-template <typename T> __device__ __forceinline__ uint64_t pxu_le(const uint8_t *q, uint32_t n) {
-    uint64_t v = 0;
-    for (uint32_t i = 0; i < n; i++) v |= (uint64_t)q[i] << (8 * i);
-    return v;
-}
 
 // ---- FTL / BASE.  BL: no index -- position, entering rungs and values and a twelve-bit length per unit come from the segment's
 // entry of the container's restart table (level 2)

@@ -74,6 +74,16 @@ inline bool lane_per_unit_shape(uint32_t tsz, uint32_t mode, uint32_t bands) {
     return bands >= 2;
 }
 
+// Waves of one window launch: 2^22 workgroups of four, well inside what a grid may hold (2^32 threads).  A batch beyond it is split in front
+// of the window that would exceed it (window_batch_plan); one window alone stays below it with 64, 32 or 21 blocks a segment (at most 2^14
+// block rows of 257 segments) ...
+constexpr uint64_t WIN_LAUNCH_WAVES = 1ull << 24;
+// ... and, for the segments of the lane-per-unit window kernels (k_dec_win_unit.hip: 64 / bands blocks, down to 4), where this says so:
+// a window has at most nbx / seg_blocks + 2 waves for each of its block rows (window_desc, qb3_win.h).  Needs nbx, nby, nblocks, seg_blocks.
+inline bool window_unit_geometry_ok(const Geometry &g) {
+    return g.seg_blocks && (uint64_t)g.nby * (g.nbx / g.seg_blocks + 2) <= WIN_LAUNCH_WAVES && g.nblocks < (1ull << 31);
+}
+
 // Results the encoder hands back to the host (device resident, copied once per encode)
 struct EncResult {
     uint64_t total_bits;
@@ -274,9 +284,7 @@ int launch_window_tail_check(const Geometry &g, uint64_t in_bits, uint32_t *stat
 // length.  launch_decode_windows takes the descriptors' host and device copies, the chunk list on the device and n + 1 zeroed status
 // words (word 0: the table's checks, call wide; word 1 + i: window i).  Does not synchronise.  Returns hipError_t as int.
 constexpr size_t WIN_DESC_BYTES = 64;
-// waves of one launch: 2^22 workgroups of four, well inside what a grid may hold (2^32 threads).  A batch beyond it is split in front
-// of the window that would exceed it; one window alone stays below it (at most 2^14 block rows of 257 segments)
-constexpr uint64_t WIN_LAUNCH_WAVES = 1ull << 24;
+// (WIN_LAUNCH_WAVES, the waves of one launch: above, at window_unit_geometry_ok)
 size_t window_batch_plan(const Geometry &g, const IxTable &ix, const WinRect *rects, void *const *dsts, size_t n, void *descs,
                          std::vector<uint32_t> &chunks, uint64_t *segments);
 int launch_decode_windows(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
@@ -300,6 +308,17 @@ bool decode_window_best_ok(const Geometry &g, const DecPlan &plan, const IxTable
 int launch_decode_window_best(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
                               void *dst, const WinRect &r, uint32_t *status, void *stream, const IxTable &ix);
 int launch_decode_windows_best(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
+                               const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
+                               uint32_t *d_status, void *stream, const IxTable &ix);
+// The window kernels of the lane-per-unit rasters and of one-band 32/64-bit rasters (k_dec_win_unit.hip): FTL / BASE rasters whose aligned
+// decode kernel is DecKernel::pxu or DecKernel::pxw and whose level-2 table (version 3) carries the twelve-bit unit lengths those kernels
+// decode a segment from alone, on a geometry one launch holds (window_unit_geometry_ok).  decode_window_unit_ok: does the raster and its
+// table qualify (the host also asks the handle's switch, QB3X_WINK_UNIT, before it takes them).  The launchers are their 16-bit
+// counterparts' in everything but the kernels; dst must be value aligned.
+bool decode_window_unit_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix);
+int launch_decode_window_unit(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
+                              void *dst, const WinRect &r, uint32_t *status, void *stream, const IxTable &ix);
+int launch_decode_windows_unit(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
                                const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
                                uint32_t *d_status, void *stream, const IxTable &ix);
 // The same from PIECES of the container (k_dec_wins_ranged.hip; api_ranged.cpp fetches them): d_pieces: npieces >= 1 pieces sorted by

@@ -1,0 +1,69 @@
+// qb3_amd/csrc/qb3_pxu.h -- what the lane-per-unit decoders share (k_dec_pxu.hip: the whole raster; qb3_win_unit.h: the window kernels): the
+// shuffle and the scan along a band, the band map as nibbles, the pieces a block's row is stored in, the little-endian fields of a table
+// entry, the LDS a wave needs, and the fill of the wave's tile.
+#pragma once
+#include "qb3_wide.h"
+
+namespace qb3dev {
+
+template <typename T> __device__ __forceinline__ T pxu_shfl(T v, uint32_t src) {
+    if constexpr (sizeof(T) == 8) return (T)__shfl((unsigned long long)v, (int)src, 64);
+    else return (T)__shfl((unsigned)v, (int)src, 64);
+}
+// exclusive scan along the lanes `stride` apart (a band's units)
+template <typename T> __device__ __forceinline__ T pxu_exscan_band(T v, uint32_t stride) {
+    const uint32_t lane = threadIdx.x & 63;
+    T x = v;
+    for (uint32_t d = stride; d < 64; d <<= 1) {
+        T y;
+        if constexpr (sizeof(T) == 8) y = (T)__shfl_up((unsigned long long)x, d, 64);
+        else y = (T)__shfl_up((unsigned)x, d, 64);
+        if (lane >= d) x = (T)(x + y);
+    }
+    return (T)(x - v);
+}
+// the band map, four bits a band (a lane indexes it by its band: kernel arguments live in scalar registers)
+__device__ __forceinline__ uint64_t pxu_band_nibbles(const DecArgs &a0) {
+    uint64_t n = 0;
+    for (uint32_t c = 0; c < (uint32_t)MAXBANDS; c++) n |= (uint64_t)(a0.g.cband[c] & 15u) << (4 * c);
+    return n;
+}
+// a piece of a block's row: sixteen, eight or four bytes, whichever divides the row's 4 x bands x value size bytes
+template <int N> struct PxuPiece;
+template <> struct PxuPiece<16> { typedef uint32_t v __attribute__((ext_vector_type(4))); };
+template <> struct PxuPiece<8> { typedef uint32_t v __attribute__((ext_vector_type(2))); };
+template <> struct PxuPiece<4> { typedef uint32_t v; };
+
+// The wave's tile, laid out like the image ([row][block][x][band], RP elements a pixel row): o[i] is the value of curve position i of
+// the lane's unit (block blk of the segment, band c of B).  The tile takes the place of the staged words, which are dead once every
+// lane holds its values; behind the fill the wave may read what any of its lanes wrote.
+template <typename T>
+__device__ __forceinline__ void pxu_tile_fill(T *tile, const T (&o)[16], bool act, uint32_t blk, uint32_t c, uint32_t B, uint32_t RP, uint64_t order) {
+    if (act) {
+        const uint32_t e0 = blk * 4 * B + c;
+#pragma unroll
+        for (uint32_t i = 0; i < 16; i++) {
+            const uint32_t nib = curve_nib(order, i);
+            tile[e0 + (nib >> 2) * RP + (nib & 3) * B] = o[i];
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// bytes of LDS a wave needs: the staged words and, in their place afterwards, the tile; then a slot per block
+// (PXU_PAD zero words behind the staged ones: what wide_values_lds reads beyond a position inside the staged bits, qb3_wide.h)
+constexpr uint32_t PXU_PAD = WIDE_PAD_DW;
+__host__ __device__ inline uint32_t pxu_wave_bytes(uint32_t in_cap_dw, uint32_t tsz) {
+    const uint32_t st = 4 * (in_cap_dw + PXU_PAD), tl = 16 * 64 * tsz;
+    return (((st > tl ? st : tl) + 15u) & ~15u) + 8 * 32;
+}
+
+template <typename T> __device__ __forceinline__ uint64_t pxu_le(const uint8_t *q, uint32_t n) {
+    uint64_t v = 0;
+    for (uint32_t i = 0; i < n; i++) v |= (uint64_t)q[i] << (8 * i);
+    return v;
+}
+
+}  // namespace qb3dev

@@ -126,7 +126,9 @@ class DeviceDecoder:
     def set_window_kernels(self, mask):
         """qb3x_set_decoder_window_kernels: rasters beyond the 8-bit ones whose window calls take a window kernel (path 1) --
         qb3_amd.QB3X_WINK_U16: 16-bit rasters of 1, 2, 3, 4, 6, 8 bands with a level-2 table; qb3_amd.QB3X_WINK_CF8: 8-bit rasters of
-        1, 3, 4 bands in the common-factor modes; the bits may be or-ed; 0 (the default): none"""
+        1, 3, 4 bands in the common-factor modes; qb3_amd.QB3X_WINK_UNIT: every other FTL / BASE raster with a level-2 table (8-bit
+        rasters of 2 or 5 to 16 bands, 16-bit rasters of an odd band count above 4, 32/64-bit rasters of any band count), destinations
+        on a multiple of the value size; the bits may be or-ed; 0 (the default): none"""
         lib.qb3x_set_decoder_window_kernels(self.p, int(mask))
 
     def decode_windows(self, d_stream, rects, out=None, index=None):

@@ -10,6 +10,10 @@ library's profile (dec_window) in a pass of its own.  One JSON line per window.
 window kernel of the common-factor modes (path 1, profile name dec_window_best).  The same call with and without the bit alternate
 in one run (window_ms against window_off_ms: the strips of path 2), and the profile pass also times the whole decode's kernel
 (dec_units) for the whole-raster window to be compared with.
+--kernels-unit CASE (u8x5, u16x7, i32x1, i64x2: 8192 x 8192 rasters of uint8 x 5, uint16 x 7, int32 x 1, int64 x 2, FTL, level-2 table; without
+CASE each in a child process of its own) times the window kernels of QB3X_WINK_UNIT: the call with the bit (path 1, profile name
+dec_window_unit) and the same call with the mask at 0 (path 2: the strips of the window's block rows, then the crop) on the same
+handle, alternating in one run, for windows of 256^2, 1024^2 and 4096^2; the kernels' own times from the profile in a pass of its own.
 Without CASE every raster runs in a child process of its own under a time limit, and the first failure ends the run; --kernels-cf
 then adds CASE best and is passed to it alone (the bit changes nothing for the other two).
 
@@ -115,6 +119,54 @@ def run(case, kernels16=False, kernels_cf=False):
         line.update(off)
         line.update({"decode_and_crop_ms": [round(t, 4) for t in t_old], "kernel_ms": kern})
         print(json.dumps(line), flush=True)
+
+
+UNIT_CASES = {"u8x5": (8192, 8192, 5, 0, "NOISY3"), "u16x7": (8192, 8192, 7, 2, "LANDSAT16"), "i32x1": (8192, 8192, 1, 5, "DEM"), "i64x2": (8192, 8192, 2, 7, "DEM")}
+
+
+def run_unit(case):
+    """path 1 under QB3X_WINK_UNIT against path 2 with the mask at 0: the same handle, the same windows, alternating"""
+    import torch
+    from qb3_amd import synth, device as qdev, TYPESIZE, QB3X_WINK_UNIT
+    w, h, b, dt, gen = UNIT_CASES[case]
+    tsz = TYPESIZE[dt]
+    img = synth.generate(w, h, b, dt, gen, 3)
+    raw = img.reshape(-1).view(torch.uint8)
+    enc = qdev.DeviceEncoder(w, h, b, dt, mode=8, want_index=False, index_chunk=2)
+    dst, n, _ = enc.encode(raw)
+    dec = qdev.DeviceDecoder(dst, n)
+    x0, y0 = 1001, 517
+    for side in (256, 1024, 4096):
+        out = torch.empty(side * side * b * tsz, dtype=torch.uint8, device="cuda")
+        crop = out.view(side, side * b * tsz)
+        want = raw.view(h, -1)[y0:y0 + side, x0 * b * tsz:(x0 + side) * b * tsz]
+
+        def window():
+            dec.decode_window(dst, x0, y0, side, side, out=out)
+
+        reps = 200 if side <= 1024 else 30
+        t, last = {1: [], 0: []}, {}
+        for _ in range(3):                              # alternating, three rounds each
+            for on in (1, 0):
+                dec.set_window_kernels(QB3X_WINK_UNIT if on else 0)
+                out.zero_()
+                window()
+                assert torch.equal(crop, want), "window bytes"
+                last[on] = dec.last_window
+                t[on].append(round(timed(window, reps), 4))
+        kern = {}
+        for on in (1, 0):
+            dec.set_window_kernels(QB3X_WINK_UNIT if on else 0)
+            qdev.profile_reset()
+            qdev.profile_enable(1)
+            for _ in range(20):
+                window()
+            torch.cuda.synchronize()
+            qdev.profile_enable(0)
+            kern.update({k: round(v[0] / v[1], 4) for k, v in qdev.profile_report().items() if k in ("dec_window_unit", "dec_units")})
+        print(json.dumps({"case": case, "raster": [w, h, b], "bytes_per_value": tsz, "container_bytes": n, "window": [x0, y0, side, side],
+                          "path": last[1][0], "segments": last[1][1], "window_ms": t[1],
+                          "path_off": last[0][0], "segments_off": last[0][1], "window_off_ms": t[0], "kernel_ms": kern}), flush=True)
 
 
 BATCH_CASES = {"batch256": (16384, 16384, 3, 2, 64, 256), "batch1024": (16384, 16384, 3, 2, 64, 1024), "batch_path3": (4096, 4096, 3, 0, 16, 256)}
@@ -270,9 +322,19 @@ def run_ranged(path, rect=None, kernels16=False, kernels_cf=False):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
-    k16, kcf = "--kernels16" in args, "--kernels-cf" in args
-    args = [a for a in args if a not in ("--kernels16", "--kernels-cf")]
-    if args and args[0] == "--ranged":
+    k16, kcf, kunit = "--kernels16" in args, "--kernels-cf" in args, "--kernels-unit" in args
+    args = [a for a in args if a not in ("--kernels16", "--kernels-cf", "--kernels-unit")]
+    if kunit:
+        if args and args[0] not in UNIT_CASES:
+            sys.exit("window_bench: --kernels-unit takes one of %s" % ", ".join(UNIT_CASES))
+        if args:
+            run_unit(args[0])
+        else:
+            for case in UNIT_CASES:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--kernels-unit", case], timeout=300)
+                if r.returncode:
+                    sys.exit("window_bench: %s ended with status %d; nothing more is run" % (case, r.returncode))
+    elif args and args[0] == "--ranged":
         if len(args) < 2:
             sys.exit("window_bench: --ranged takes a file (and, optionally, x0,y0,w,h)")
         run_ranged(args[1], tuple(int(v) for v in args[2].split(",")) if len(args) > 2 else None, k16, kcf)
