@@ -86,7 +86,15 @@ size_t qb3x_decode_device(decsp p, const void *d_src, void *d_dst, const void *d
  *      reporting, and no scratch raster on a handle that only ever takes path 1.  A raster so large that one window could need more
  *      waves than a launch holds -- more than 2^24 for blocks per column x (blocks per row / blocks per segment + 2), which takes 16 or
  *      fewer blocks a segment and a side beyond 2^15 pixels -- or of 2^31 blocks and more goes as below.  The common-factor modes of these
- *      shapes are not taken.
+ *      shapes are not taken by this bit.
+ *      With QB3X_WINK_CFU path 1 takes them: the common-factor streams (QB3M_CF, QB3M_CF_H; QB3M_BEST / QB3M_CF_RLE where the RLE0
+ *      pass did not win) of 8-bit rasters of 2 or of 5 to 16 bands, of 16-bit rasters of 2 and more bands, of 32/64-bit rasters of any
+ *      band count and of one-band 16-bit rasters, from a table of version 3, level 1 or 2, with its three-byte field per unit (an
+ *      entry has 6 + bands * (1 + 2 * value size) + 3 * (64 / bands) * bands bytes), d_index NULL, d_dst on a multiple of the value
+ *      size: 64 / bands blocks a segment (64 for one band), the same limits on the raster's size, the same reporting, no scratch
+ *      raster on a handle that only ever takes path 1.  Trust is as under QB3X_WINK_CF8: under a table whose check was sealed again
+ *      the kernel cross-checks what the whole decode from the table cross-checks -- positions, unit lengths, entering rungs -- not an
+ *      entry's entering value or factor, which both take as they are and turn into the same pixels.
  *   2  every other raster with a level-2 table (16-bit, 32/64-bit, other band counts, the common-factor modes): the segments of the
  *      window's block ROWS are decoded into a scratch raster the handle owns, then cropped.  Time follows the window's rows; the
  *      scratch is raster sized (qb3_decoded_size bytes of device memory).
@@ -121,7 +129,8 @@ size_t qb3x_last_window_segments(const decsp p);
  * read a 16-bit raster the kernels take in pieces (below), without it whole, and with QB3X_WINK_CF8 an 8-bit common-factor raster
  * the kernels take.  QB3X_WINK_UNIT adds NO ranged shortcut: on a handle of qb3x_open_ranged a raster only that bit's kernels take is
  * still read whole, once, after which its windows go the way of qb3x_decode_windows_device -- with the bit, path 1 from the uploaded
- * container (decoding these rasters from fetched pieces is not built).  Unknown bits are ignored; a NULL handle: no-op.  The bytes written are the same with and without a bit: the bit
+ * container (decoding these rasters from fetched pieces is not built).  QB3X_WINK_CFU adds none either, exactly as QB3X_WINK_UNIT:
+ * the container is read whole, once, and its windows then take path 1 from the uploaded copy.  Unknown bits are ignored; a NULL handle: no-op.  The bytes written are the same with and without a bit: the bit
  * only chooses the way.  Harmless on a handle whose raster the kernels of the bits set do not take (other value sizes, other band
  * counts, other modes, a container whose RLE0 pass won, STORED containers, narrow images, a table without block fields, an
  * out-of-band d_index): such a raster goes, and on a ranged handle is read, as it does with the mask at 0.
@@ -131,6 +140,7 @@ size_t qb3x_last_window_segments(const decsp p);
 #define QB3X_WINK_U16 1u   /* 16-bit rasters of 1, 2, 3, 4, 6, 8 bands, FTL / BASE, level-2 table: window kernel (path 1) instead of strips (path 2); ranged handles: pieces instead of the whole container */
 #define QB3X_WINK_CF8 2u   /* 8-bit rasters of 1, 3, 4 bands in the common-factor modes (QB3M_CF, QB3M_CF_H; QB3M_BEST / QB3M_CF_RLE where the RLE0 pass did not win), table of version 3 with block fields (level 1 or 2): window kernel (path 1) instead of strips (path 2); ranged handles: pieces instead of the whole container */
 #define QB3X_WINK_UNIT 4u  /* every other FTL / BASE raster with a level-2 table of version 3 -- 8-bit rasters of 2 or 5 to 16 bands, 16-bit rasters of 5, 7, 9, ... bands, 32/64-bit rasters of 1 to 16 bands: window kernel (path 1) instead of strips (path 2); ranged handles: no shortcut of its own (the container is read whole, once; its windows then take path 1) */
+#define QB3X_WINK_CFU 8u   /* the common-factor streams (QB3M_CF, QB3M_CF_H; QB3M_BEST / QB3M_CF_RLE where the RLE0 pass did not win) of those shapes and of one-band 16-bit rasters -- 8-bit rasters of 2 or 5 to 16 bands, 16-bit rasters of 2 and more bands, 16/32/64-bit rasters of one band, 32/64-bit rasters of several -- with a table of version 3 (level 1 or 2) that carries a field per unit: window kernel (path 1) instead of strips (path 2); ranged handles: no shortcut of its own, as QB3X_WINK_UNIT */
 void qb3x_set_decoder_window_kernels(decsp p, unsigned mask);
 
 /* A batch of windows: n rectangles of ONE raster in one call -- what a tile server, a viewer or a cropping loader asks of a raster
@@ -357,7 +367,7 @@ size_t qb3_decode(decsp p, void *destination);                                  
  * events on the launch stream; totals are resolved at the library's own synchronisation points.
  * Kernel names: enc_units, enc_scan, enc_concat, enc_seams, enc_best_units, enc_best_scan, enc_best_recode,
  * dec_index_table, dec_index_serial, dec_index_prev, dec_index_scan, dec_units, dec_segments, dec_window (the window kernel of
- * qb3x_decode_window_device, path 1), dec_window16 (the 16-bit window kernels: path 1 under QB3X_WINK_U16), dec_window_best (the window kernels of the 8-bit common-factor modes: path 1 under QB3X_WINK_CF8), dec_window_unit (the window kernels of the lane-per-unit and one-band 32/64-bit rasters: path 1 under QB3X_WINK_UNIT), dec_window_ranged (the same from fetched pieces: the ranged calls), dec_window16_ranged (... of 16-bit rasters under QB3X_WINK_U16), dec_window_best_ranged (... of 8-bit common-factor rasters under QB3X_WINK_CF8), reindex_fill, reindex_finish (qb3x_reindex_device: the table's entries; everything else of the
+ * qb3x_decode_window_device, path 1), dec_window16 (the 16-bit window kernels: path 1 under QB3X_WINK_U16), dec_window_best (the window kernels of the 8-bit common-factor modes: path 1 under QB3X_WINK_CF8), dec_window_unit (the window kernels of the lane-per-unit and one-band 32/64-bit rasters: path 1 under QB3X_WINK_UNIT), dec_window_best_unit (those of the common-factor streams of such shapes: path 1 under QB3X_WINK_CFU), dec_window_ranged (the same from fetched pieces: the ranged calls), dec_window16_ranged (... of 16-bit rasters under QB3X_WINK_U16), dec_window_best_ranged (... of 8-bit common-factor rasters under QB3X_WINK_CF8), reindex_fill, reindex_finish (qb3x_reindex_device: the table's entries; everything else of the
  * new container).
  * level: 0 off, 1 every kernel, 2 all but the microsecond kernels (enc_scan, enc_seams, enc_best_scan), whose two
  * events cost more than they take. */

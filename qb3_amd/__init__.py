@@ -34,6 +34,7 @@ QB3X_REF_CBAND0 = 1
 QB3X_WINK_U16 = 1           # qb3x_set_decoder_window_kernels: the 16-bit window kernels
 QB3X_WINK_CF8 = 2           # ... the window kernels of the 8-bit common-factor modes (1, 3, 4 bands)
 QB3X_WINK_UNIT = 4          # ... the window kernels of the lane-per-unit rasters and of one-band 32/64-bit rasters (FTL / BASE)
+QB3X_WINK_CFU = 8           # ... the window kernels of the common-factor streams of such shapes and of one-band 16-bit rasters
 TYPESIZE = (1, 1, 2, 2, 4, 4, 8, 8)
 
 _vp, _sz, _u64 = C.c_void_p, C.c_size_t, C.c_uint64
@@ -325,8 +326,8 @@ class RangedReader:
     def set_window_kernels(self, mask):
         """qb3x_set_decoder_window_kernels on the ranged handle: QB3X_WINK_U16 -- 16-bit rasters of 1, 2, 3, 4, 6, 8 bands with a
         level-2 table are read in pieces too (else they are read whole, every call); QB3X_WINK_CF8 -- so are 8-bit rasters of 1, 3, 4
-        bands in the common-factor modes whose table carries block fields; QB3X_WINK_UNIT adds no ranged shortcut (the container is
-        read whole, once; its windows then take the window kernel from the uploaded copy); 0 (the default): none"""
+        bands in the common-factor modes whose table carries block fields; QB3X_WINK_UNIT and QB3X_WINK_CFU add no ranged shortcut (the
+        container is read whole, once; its windows then take the window kernel from the uploaded copy); 0 (the default): none"""
         lib.qb3x_set_decoder_window_kernels(self.p, int(mask))
 
     def set_gap(self, nbytes):

@@ -14,7 +14,8 @@ using namespace qb3api;
 //           On a handle that asked for them (qb3x_set_decoder_window_kernels, QB3X_WINK_U16) also 16-bit rasters of 1, 2, 3, 4, 6 or
 //           8 bands, through the kernels of k_dec_win16.hip, and (QB3X_WINK_CF8) 8-bit rasters of 1, 3 or 4 bands in the common-factor
 //           modes, through those of k_dec_win_best.hip, and (QB3X_WINK_UNIT) the FTL / BASE rasters of the lane-per-unit decoder and
-//           one-band 32/64-bit rasters, through those of k_dec_win_unit.hip (WinFamily: what the two functions below pick their launcher by);
+//           one-band 32/64-bit rasters, through those of k_dec_win_unit.hip, and (QB3X_WINK_CFU) the common-factor streams of such shapes and
+//           of one-band 16-bit rasters, through those of k_dec_win_best_unit.hip (WinFamily: what the two functions below pick their launcher by);
 //   path 2  every other raster that decodes strip by strip (decode_strips_ok): the windows' block rows as ranges of segments, merged
 //           so that a segment is decoded once, into the handle's scratch raster, then a crop per window;
 //   path 3  ONE whole decode with its fallback ladder into the scratch raster for all windows that have no pixels yet, then their crops.
@@ -59,13 +60,14 @@ static WinSrc window_source(const decs *p, const Geometry &g, const void *d_src)
 }
 
 // the kernels path 1 goes through, and their launchers: the single call's and the batch's
-enum class WinFamily { none, u8, u16, cf8, unit };
+enum class WinFamily { none, u8, u16, cf8, unit, cfu };
 static const struct {
     int (*one)(const Geometry &, const DecPlan &, const uint32_t *, uint32_t, uint64_t, void *, const WinRect &, uint32_t *, void *, const IxTable &);
     int (*batch)(const Geometry &, const DecPlan &, const uint32_t *, uint32_t, uint64_t, const void *, const void *, size_t, const uint32_t *, size_t, uint32_t *, void *, const IxTable &);
 } win_launchers[] = {      // in WinFamily's order
     { nullptr, nullptr }, { launch_decode_window, launch_decode_windows }, { launch_decode_window16, launch_decode_windows16 },
-    { launch_decode_window_best, launch_decode_windows_best }, { launch_decode_window_unit, launch_decode_windows_unit } };
+    { launch_decode_window_best, launch_decode_windows_best }, { launch_decode_window_unit, launch_decode_windows_unit },
+    { launch_decode_window_best_unit, launch_decode_windows_best_unit } };
 
 // The three functions below mark the windows they gave their pixels (paths[i]) and count the segments they decoded; false: a HIP failure.
 // path 1, the single call: the window as kernel arguments, one status word back
@@ -156,10 +158,13 @@ size_t qb3api::windows_device(decsp p, const void *d_src, const void *d_index, c
         // the lane-per-unit window kernels: a handle that asked, a raster and table they take, value-aligned stores to every destination
         bool unit = (p->win_kernels & QB3X_WINK_UNIT) && decode_window_unit_ok(g, s.plan, s.ixt);
         for (size_t i = 0; unit && i < n; i++) unit = ((uintptr_t)wins[i].dst & (g.tsz - 1)) == 0;
-        // the common-factor window kernels: a handle that asked, a raster and table they take; byte stores, any destination
+        // ... and those of the common-factor streams of such shapes: the same
+        bool cfu = (p->win_kernels & QB3X_WINK_CFU) && decode_window_best_unit_ok(g, s.plan, s.ixt);
+        for (size_t i = 0; cfu && i < n; i++) cfu = ((uintptr_t)wins[i].dst & (g.tsz - 1)) == 0;
+        // the 8-bit common-factor window kernels: a handle that asked, a raster and table they take; byte stores, any destination
         const WinFamily fam = wide ? WinFamily::u16 : decode_window_ok(g, s.plan, s.ixt) ? WinFamily::u8
                             : (p->win_kernels & QB3X_WINK_CF8) && decode_window_best_ok(g, s.plan, s.ixt) ? WinFamily::cf8
-                            : unit ? WinFamily::unit : WinFamily::none;
+                            : unit ? WinFamily::unit : cfu ? WinFamily::cfu : WinFamily::none;
         if (fam != WinFamily::none) {
             if (!(single ? window_kernel_one(p, s, wins[0], paths, &segs, st, fam) : window_kernel_batch(p, s, wins, n, paths, &segs, st, fam))) return fail();
         } else if ((scratch = decode_strips_ok(g, s.plan, s.ixt))) {

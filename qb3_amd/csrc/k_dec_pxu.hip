@@ -245,48 +245,11 @@ __global__ void __launch_bounds__(256) dec_pxu_best_kernel(const DecArgs a0) {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
-    const uint32_t limit = 32 * ndw;
     const uint32_t cpos = (uint32_t)(a.in_bit0 + P0 - 32 * w0);
     bool bad = !fits;
-    const uint32_t blen = bt & 0xffffu, oldrung = (bt >> 16) & UMASK;
-    const uint32_t binc = wave_iscan32(blen);
-    uint32_t pos = cpos + binc - blen;
-    pos = pos < limit ? pos : limit;
-    // the rung the band's NEXT unit is entered with is the rung this unit must leave: checked, not trusted
-    const uint32_t nxt = (uint32_t)__shfl_down((unsigned)(bt >> 16), B, 64);
-    uint64_t period = 0;                                            // lanes 0, B, 2B, ...: shifted by its band, a lane's band
-    for (uint32_t k = 0; k < 64; k += B) period |= 1ull << k;
-    T g[16], pcf = cf0, cf_in = cf0;
-#pragma unroll
-    for (int i = 0; i < 16; i++) g[i] = 0;
-    uint32_t rung = oldrung, flags = 0, end = pos;
-    bool ok = true, need = act;
-#pragma nounroll
-    for (int pass = 0; pass < 2; pass++) {
-        if (need) {
-            ReaderT<LdsWords> rd;
-            rd.init((LdsWords)stage, pos, 32ull * (ndw + PXU_PAD));
-            rung = oldrung; pcf = cf_in; flags = 0;
-            ok = parse_unit<T, CM_BEST, ReaderT<LdsWords>>(rd, rung, pcf, g, &flags);
-            end = (uint32_t)rd.position();
-        }
-        if (pass) break;
-        // the factor in force for a unit that takes the band's: the nearest lane of the band below whose unit brought one
-        const uint64_t wm = __ballot(act && (flags & 2u));
-        if (!wm) break;                                             // (no writer in the segment: every lane assumed right)
-        const uint64_t below = wm & (period << c) & ((1ull << lane) - 1);
-        const uint32_t src = below ? 63u - (uint32_t)__clzll((long long)below) : lane;
-        const T got = pxu_shfl<T>(pcf, src);
-        need = act && (flags & 1u) && below && got != cf0;
-        cf_in = got;
-        if (!__any(need)) break;
-    }
-    if (act && (!ok || end != pos + blen)) bad = true;              // malformed unit, or the lengths are not this stream's
-    if (act && blk + 1 < nb_here && rung != (nxt & UMASK)) bad = true;
-    T run[16], acc = 0;
-#pragma unroll
-    for (int i = 0; i < 16; i++) { acc = (T)(acc + smag_t<T>(g[i])); run[i] = acc; }
-    const T usum = act ? acc : (T)0;
+    T run[16];
+    const uint32_t binc = pxu_best_units<T>(stage, ndw, cpos, bt, cf0, act, blk, c, B, nb_here, run, bad);
+    const T usum = act ? run[15] : (T)0;
     const T sex = pxu_exscan_band<T>(usum, B);
     if (bad) atomicOr(a.status, fits ? 1u : misfit);
     if (a.totals_only) {    // a plain stream, first pass: the segment's per-band sums (prev_scan_kernel makes entering values of them)

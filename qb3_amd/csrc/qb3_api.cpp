@@ -511,7 +511,7 @@ QB3_API void qb3_destroy_decoder(decsp p) {
 }
 QB3_API void qb3_set_decoder_stride(decsp p, size_t stride) { p->stride = stride; }
 QB3_API void qb3x_set_decoder_compat(decsp p, unsigned flags) { if (p) p->compat = flags; }
-QB3_API void qb3x_set_decoder_window_kernels(decsp p, unsigned mask) { if (p) p->win_kernels = mask & (QB3X_WINK_U16 | QB3X_WINK_CF8 | QB3X_WINK_UNIT); }
+QB3_API void qb3x_set_decoder_window_kernels(decsp p, unsigned mask) { if (p) p->win_kernels = mask & (QB3X_WINK_U16 | QB3X_WINK_CF8 | QB3X_WINK_UNIT | QB3X_WINK_CFU); }
 
 // A plain 8-bit stream (no index, no restart table) is walked through a table in device memory (qb3_dev.h): make sure
 // the decoder holds one -- the whole call in one round, or walk_table_cap() and several rounds.  False: out of memory.

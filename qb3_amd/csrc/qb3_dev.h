@@ -321,6 +321,17 @@ int launch_decode_window_unit(const Geometry &g, const DecPlan &plan, const uint
 int launch_decode_windows_unit(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
                                const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
                                uint32_t *d_status, void *stream, const IxTable &ix);
+// The window kernels of the common-factor streams of such shapes (k_dec_win_best_unit.hip): rasters in CM_BEST whose aligned decode kernel
+// is DecKernel::pxu_best or DecKernel::pxw_best and whose table (level 1 or 2, version 3) carries the three-byte field per unit those
+// kernels decode a segment from alone, on a geometry one launch holds.  decode_window_best_unit_ok: does the raster and its table qualify
+// (the host also asks the handle's switch, QB3X_WINK_CFU, before it takes them).  The launchers are launch_decode_window_unit's and
+// launch_decode_windows_unit's in everything but the kernels; dst must be value aligned.
+bool decode_window_best_unit_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix);
+int launch_decode_window_best_unit(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
+                                   void *dst, const WinRect &r, uint32_t *status, void *stream, const IxTable &ix);
+int launch_decode_windows_best_unit(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
+                                    const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
+                                    uint32_t *d_status, void *stream, const IxTable &ix);
 // The same from PIECES of the container (k_dec_wins_ranged.hip; api_ranged.cpp fetches them): d_pieces: npieces >= 1 pieces sorted by
 // first segment, each a run of consecutive segments { seg0, nseg, ent0, word0, stream word of its first packed word (low, high),
 // nwords, 0 }; d_entries: the compact array of table entries (ix.entry_bytes each), nseg + 1 per piece from index ent0; d_words: the

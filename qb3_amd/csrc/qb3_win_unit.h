@@ -31,6 +31,61 @@ __device__ __forceinline__ void winu_store_whole(uint8_t *dst, const uint8_t *ti
     }
 }
 
+// The wave's values to the window, once every lane holds its sixteen (o[i]: curve position i of the lane's unit, block blk of the segment,
+// band c): through the wave's LDS tile at wmem, which takes the place of the staged words; g0: the segment's first block, nb_here: its
+// blocks.  Whole blocks go row by row in pieces (winu_store_whole), edge blocks value by value under their column mask.  Both wave
+// routines call it: winu_decode_wave below and winu_best_decode_wave (qb3_win_best_unit.h).
+template <typename T>
+__device__ __forceinline__ void winu_store_tile(const DecArgs &a, const WinDesc &w, uint8_t *wmem, const T (&o)[16], bool act, uint32_t blk, uint32_t c,
+                                                uint32_t g0, uint32_t nb_here) {
+    const uint32_t lane = threadIdx.x & 63, NB = a.g.seg_blocks, nbx = a.g.nbx, B = a.g.bands;      // NB * B <= 64
+    // every lane holds its sixteen values in registers: the tile takes the place of the staged words
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const uint32_t RP = NB * 4 * B;                     // tile elements per pixel row
+    pxu_tile_fill<T>((T *)wmem, o, act, blk, c, B, RP, a.g.order);
+
+    // lane L describes block L of the segment: is it one of the window's, which of its rows and columns are its own (a shifted last
+    // block repeats pixels of its neighbour, which holds them by the rule) and inside the window, where its first pixel goes
+    uint32_t info = 0;
+    int64_t off = 0;
+    if (lane < nb_here) {
+        const uint32_t g = g0 + lane, by = g / nbx, bx = g - by * nbx;
+        if (bx >= w.bx0 && bx <= w.bx1 && by >= w.by0 && by <= w.by1) {
+            const uint32_t xb = (4 * bx + 4 > a.g.w) ? a.g.w - 4 : 4 * bx;     // last column / row is shifted, not padded
+            const uint32_t yb = (4 * by + 4 > a.g.h) ? a.g.h - 4 : 4 * by;
+            uint32_t rows = 0, cols = 0;
+#pragma unroll
+            for (uint32_t t = 0; t < 4; t++) {
+                rows |= (yb + t >= 4 * by && yb + t >= w.wy0 && yb + t < w.wy1) ? 1u << t : 0u;
+                cols |= (xb + t >= 4 * bx && xb + t >= w.wx0 && xb + t < w.wx1) ? 1u << t : 0u;
+            }
+            info = rows ? rows | cols << 4 | (cols == 15u ? 0x100u : 0u) : 0u;
+            off = ((int64_t)yb - (int64_t)w.wy0) * (int64_t)w.dstride + ((int64_t)xb - (int64_t)w.wx0) * (int64_t)(B * sizeof(T));
+        }
+    }
+    const uint32_t RB = 4 * B * (uint32_t)sizeof(T), RPB = RP * (uint32_t)sizeof(T);      // bytes of a block's row (a multiple of 4), of a tile row
+    if (__any((int)(info & 0x100u))) {
+        if ((RB & 15) == 0) winu_store_whole<16, T>(w.dst, wmem, off, info, w.dstride, nb_here * (RB >> 4), RB >> 4, RB, RPB);
+        else if ((RB & 7) == 0) winu_store_whole<8, T>(w.dst, wmem, off, info, w.dstride, nb_here * (RB >> 3), RB >> 3, RB, RPB);
+        else winu_store_whole<4, T>(w.dst, wmem, off, info, w.dstride, nb_here * (RB >> 2), RB >> 2, RB, RPB);
+    }
+    if (__any((int)(info && !(info & 0x100u)))) {       // edge blocks: the values of the window's columns, one by one
+        const T *tile = (const T *)wmem;
+        const uint32_t n = nb_here * 4 * B;
+        for (uint32_t j0 = 0; j0 < n; j0 += 64) {
+            const uint32_t j = j0 + lane, eb = j / (4 * B), rem = j - eb * 4 * B, x = fastdiv(rem, B, a.magic_bands);
+            const uint32_t bi = pxu_shfl<uint32_t>(info, eb & 63u);
+            const int64_t bo = (int64_t)pxu_shfl<uint64_t>((uint64_t)off, eb & 63u);
+            if (j >= n || (bi & 0x100u) || !((bi >> (4 + x)) & 1u)) continue;
+#pragma unroll
+            for (uint32_t y = 0; y < 4; y++)
+                if ((bi >> y) & 1u) ((T *)(w.dst + bo + (int64_t)((uint64_t)y * w.dstride)))[rem] = tile[y * RP + j];
+        }
+    }
+}
+
 // Wave `wid` of window w (wave: its number in the workgroup of four; both wave uniform).  status: the word this window's failures go to.
 // Every wave of the workgroup comes here (there is one workgroup barrier); smem: the launch's dynamic LDS: the 2 KB code table, then
 // pxu_wave_bytes a wave, sized for the WORST-CASE segment (a.in_cap_dw = the plan's px_cap_dw): a segment that does not fit is not this
@@ -131,51 +186,7 @@ __device__ __forceinline__ void winu_decode_wave(const DecArgs &a, const WinDesc
 #pragma unroll
         for (int i = 0; i < 16; i++) { const T v = pxu_shfl<T>(o[i], from); if (cb != c) o[i] = (T)(o[i] + v); }
     }
-    // every lane holds its sixteen values in registers: the tile takes the place of the staged words
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const uint32_t RP = NB * 4 * B;                     // tile elements per pixel row
-    pxu_tile_fill<T>((T *)wmem, o, act, blk, c, B, RP, a.g.order);
-
-    // lane L describes block L of the segment: is it one of the window's, which of its rows and columns are its own (a shifted last
-    // block repeats pixels of its neighbour, which holds them by the rule) and inside the window, where its first pixel goes
-    uint32_t info = 0;
-    int64_t off = 0;
-    if (lane < nb_here) {
-        const uint32_t g = g0 + lane, by = g / nbx, bx = g - by * nbx;
-        if (bx >= w.bx0 && bx <= w.bx1 && by >= w.by0 && by <= w.by1) {
-            const uint32_t xb = (4 * bx + 4 > a.g.w) ? a.g.w - 4 : 4 * bx;     // last column / row is shifted, not padded
-            const uint32_t yb = (4 * by + 4 > a.g.h) ? a.g.h - 4 : 4 * by;
-            uint32_t rows = 0, cols = 0;
-#pragma unroll
-            for (uint32_t t = 0; t < 4; t++) {
-                rows |= (yb + t >= 4 * by && yb + t >= w.wy0 && yb + t < w.wy1) ? 1u << t : 0u;
-                cols |= (xb + t >= 4 * bx && xb + t >= w.wx0 && xb + t < w.wx1) ? 1u << t : 0u;
-            }
-            info = rows ? rows | cols << 4 | (cols == 15u ? 0x100u : 0u) : 0u;
-            off = ((int64_t)yb - (int64_t)w.wy0) * (int64_t)w.dstride + ((int64_t)xb - (int64_t)w.wx0) * (int64_t)(B * sizeof(T));
-        }
-    }
-    const uint32_t RB = 4 * B * (uint32_t)sizeof(T), RPB = RP * (uint32_t)sizeof(T);      // bytes of a block's row (a multiple of 4), of a tile row
-    if (__any((int)(info & 0x100u))) {
-        if ((RB & 15) == 0) winu_store_whole<16, T>(w.dst, wmem, off, info, w.dstride, nb_here * (RB >> 4), RB >> 4, RB, RPB);
-        else if ((RB & 7) == 0) winu_store_whole<8, T>(w.dst, wmem, off, info, w.dstride, nb_here * (RB >> 3), RB >> 3, RB, RPB);
-        else winu_store_whole<4, T>(w.dst, wmem, off, info, w.dstride, nb_here * (RB >> 2), RB >> 2, RB, RPB);
-    }
-    if (__any((int)(info && !(info & 0x100u)))) {       // edge blocks: the values of the window's columns, one by one
-        const T *tile = (const T *)wmem;
-        const uint32_t n = nb_here * 4 * B;
-        for (uint32_t j0 = 0; j0 < n; j0 += 64) {
-            const uint32_t j = j0 + lane, eb = j / (4 * B), rem = j - eb * 4 * B, x = fastdiv(rem, B, a.magic_bands);
-            const uint32_t bi = pxu_shfl<uint32_t>(info, eb & 63u);
-            const int64_t bo = (int64_t)pxu_shfl<uint64_t>((uint64_t)off, eb & 63u);
-            if (j >= n || (bi & 0x100u) || !((bi >> (4 + x)) & 1u)) continue;
-#pragma unroll
-            for (uint32_t y = 0; y < 4; y++)
-                if ((bi >> y) & 1u) ((T *)(w.dst + bo + (int64_t)((uint64_t)y * w.dstride)))[rem] = tile[y * RP + j];
-        }
-    }
+    winu_store_tile<T>(a, w, wmem, o, act, blk, c, g0, nb_here);
     if (bad) atomicOr(status, fits ? 1u : 8u);
     // a segment that reaches beyond the stream's end (a stream cut short): the whole-raster decode decides what its pixels are
     if (lane == 0 && (P1 > a.in_bits || P1 < P0)) atomicOr(status, 4u);

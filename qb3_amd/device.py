@@ -128,7 +128,8 @@ class DeviceDecoder:
         qb3_amd.QB3X_WINK_U16: 16-bit rasters of 1, 2, 3, 4, 6, 8 bands with a level-2 table; qb3_amd.QB3X_WINK_CF8: 8-bit rasters of
         1, 3, 4 bands in the common-factor modes; qb3_amd.QB3X_WINK_UNIT: every other FTL / BASE raster with a level-2 table (8-bit
         rasters of 2 or 5 to 16 bands, 16-bit rasters of an odd band count above 4, 32/64-bit rasters of any band count), destinations
-        on a multiple of the value size; the bits may be or-ed; 0 (the default): none"""
+        on a multiple of the value size; qb3_amd.QB3X_WINK_CFU: the common-factor streams of those shapes and of one-band 16-bit
+        rasters, the same destinations; the bits may be or-ed; 0 (the default): none"""
         lib.qb3x_set_decoder_window_kernels(self.p, int(mask))
 
     def decode_windows(self, d_stream, rects, out=None, index=None):

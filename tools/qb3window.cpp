@@ -3,7 +3,7 @@
 // table (cqb3x with QB3X_INDEX_CHUNK=2, qb3index -2) is read in pieces -- an 8-bit FTL / BASE one always, a 16-bit one with -k, an
 // 8-bit common-factor one with -K; any other file is read whole and gives the same pixels.
 //
-//   qb3window [-v] [-k] [-K] [-u] [-g gap] in.qb3 x0,y0,w,h out.pnm
+//   qb3window [-v] [-k] [-K] [-u] [-U] [-g gap] in.qb3 x0,y0,w,h out.pnm
 //
 //   -g gap  merge two byte ranges that lie at most `gap` bytes apart (fewer reads, more bytes; default 0)
 //   -k      16-bit files too are read in pieces (qb3x_set_decoder_window_kernels, QB3X_WINK_U16)
@@ -11,6 +11,7 @@
 //           without it such a file is read whole
 //   -u      sets QB3X_WINK_UNIT: no file is read in pieces for it, but the window of a file the lane-per-unit window kernels take (a
 //           32-bit one-band file, say) is then decoded by them from the file read whole, not through a raster-sized scratch buffer
+//   -U      sets QB3X_WINK_CFU: the same for the common-factor modes of such files (a 16-bit grey or RGB file written with cqb3x -b, say)
 //   -v      prints bytes read and calls of the reader against the file's size
 #include "qb3x.h"
 #include <cstdint>
@@ -24,9 +25,10 @@
 
 namespace {
 
-const char *USAGE = "qb3window [-v] [-k] [-K] [-u] [-g gap] in.qb3 x0,y0,w,h out.pnm\n"
+const char *USAGE = "qb3window [-v] [-k] [-K] [-u] [-U] [-g gap] in.qb3 x0,y0,w,h out.pnm\n"
                     "  -k  read 16-bit files in pieces too    -K  read 8-bit common-factor files (cqb3x -b) in pieces too\n"
-                    "  -u  window kernels for files read whole (QB3X_WINK_UNIT)\n";
+                    "  -u  window kernels for files read whole (QB3X_WINK_UNIT)\n"
+                    "  -U  ... and for their common-factor modes (QB3X_WINK_CFU)\n";
 
 int fail(const std::string &msg) {
     fprintf(stderr, "qb3window: %s\n", msg.c_str());
@@ -48,7 +50,7 @@ int read_at(void *ctx, uint64_t offset, void *dst, size_t size) {
 }  // namespace
 
 int main(int argc, char **argv) {
-    bool verbose = false, kernels16 = false, kernels_cf = false, kernels_unit = false;
+    bool verbose = false, kernels16 = false, kernels_cf = false, kernels_unit = false, kernels_cfu = false;
     size_t gap = 0;
     std::vector<std::string> names;
     for (int i = 1; i < argc; i++) {
@@ -57,6 +59,7 @@ int main(int argc, char **argv) {
         else if (a == "-k") kernels16 = true;
         else if (a == "-K") kernels_cf = true;
         else if (a == "-u") kernels_unit = true;
+        else if (a == "-U") kernels_cfu = true;
         else if (a == "-g" && i + 1 < argc) gap = (size_t)strtoull(argv[++i], nullptr, 10);
         else if (!a.empty() && a[0] == '-') { fputs(USAGE, stderr); return 2; }
         else names.push_back(a);
@@ -78,7 +81,7 @@ int main(int argc, char **argv) {
         std::vector<uint8_t> pix(w * h * dims[2] * tsz);
         const qb3x_window win = { (size_t)x0, (size_t)y0, (size_t)w, (size_t)h, pix.data(), 0 };
         qb3x_set_ranged_gap(d, gap);
-        qb3x_set_decoder_window_kernels(d, (kernels16 ? QB3X_WINK_U16 : 0u) | (kernels_cf ? QB3X_WINK_CF8 : 0u) | (kernels_unit ? QB3X_WINK_UNIT : 0u));
+        qb3x_set_decoder_window_kernels(d, (kernels16 ? QB3X_WINK_U16 : 0u) | (kernels_cf ? QB3X_WINK_CF8 : 0u) | (kernels_unit ? QB3X_WINK_UNIT : 0u) | (kernels_cfu ? QB3X_WINK_CFU : 0u));
         if (qb3x_read_windows_ranged(d, &win, 1) != 1) ret = fail(std::string("the window was not read: ") + qb3x_last_error());
         else {
             if (tsz == 2) for (size_t i = 0; i + 1 < pix.size(); i += 2) std::swap(pix[i], pix[i + 1]);     // PNM samples are big endian

@@ -16,6 +16,11 @@ dec_window_unit) and the same call with the mask at 0 (path 2: the strips of the
 handle, alternating in one run, for windows of 256^2, 1024^2 and 4096^2; the kernels' own times from the profile in a pass of its own.
 Without CASE every raster runs in a child process of its own under a time limit, and the first failure ends the run; --kernels-cf
 then adds CASE best and is passed to it alone (the bit changes nothing for the other two).
+best --kernels-cfu [SHAPE] is the best workload for the other common-factor rasters (SHAPE u16x8, u8x5, i32x1, i64x2: 8192 x 8192 rasters
+of uint16 x 8 in QB3M_CF_H, uint8 x 5 and int32 x 1 in QB3M_BEST, int64 x 2 in QB3M_CF -- generated rasters quantised to multiples of
+a factor; without SHAPE each in a child process of its own): QB3X_WINK_CFU (path 1, profile name dec_window_best_unit) against the
+mask at 0 on the same handle, as --kernels-unit measures, for windows of 256^2, 512^2 and 2048^2 and one of 8192 x 512 (whole block rows), and for each
+square side a batch of 64 windows at seeded random origins (qb3x_decode_windows_device: batch_ms against batch_off_ms).
 
 tools/window_bench.py --batch [CASE] -- the batch call (qb3x_decode_windows_device) against the same windows through single calls on
 the same handle: 64 windows of 256^2 and 64 of 1024^2 of the headline raster at seeded random origins that are not multiples of 256
@@ -121,34 +126,43 @@ def run(case, kernels16=False, kernels_cf=False):
         print(json.dumps(line), flush=True)
 
 
+# SHAPE: width, height, bands, type, generator, mode (QB3M_CF_H 5, QB3M_BEST 7, QB3M_CF 1), the factor the values are multiples of
+CFU_CASES = {"u16x8": (8192, 8192, 8, 2, "LANDSAT16", 5, 10), "u8x5": (8192, 8192, 5, 0, "NOISY3", 7, 6), "i32x1": (8192, 8192, 1, 5, "DEM", 7, 1000),
+             "i64x2": (8192, 8192, 2, 7, "DEM", 1, 2 ** 20 + 1)}
 UNIT_CASES = {"u8x5": (8192, 8192, 5, 0, "NOISY3"), "u16x7": (8192, 8192, 7, 2, "LANDSAT16"), "i32x1": (8192, 8192, 1, 5, "DEM"), "i64x2": (8192, 8192, 2, 7, "DEM")}
 
 
-def run_unit(case):
-    """path 1 under QB3X_WINK_UNIT against path 2 with the mask at 0: the same handle, the same windows, alternating"""
+def run_unit(case, cfu=False):
+    """path 1 under QB3X_WINK_UNIT (cfu: QB3X_WINK_CFU, and a batch of 64 windows too) against path 2 with the mask at 0: the same
+    handle, the same windows, alternating"""
+    import numpy as np
     import torch
-    from qb3_amd import synth, device as qdev, TYPESIZE, QB3X_WINK_UNIT
-    w, h, b, dt, gen = UNIT_CASES[case]
+    from qb3_amd import synth, device as qdev, TYPESIZE, QB3X_WINK_UNIT, QB3X_WINK_CFU
+    w, h, b, dt, gen, mode, factor = CFU_CASES[case] if cfu else UNIT_CASES[case] + (8, 1)
+    bit, kname = (QB3X_WINK_CFU, "dec_window_best_unit") if cfu else (QB3X_WINK_UNIT, "dec_window_unit")
     tsz = TYPESIZE[dt]
     img = synth.generate(w, h, b, dt, gen, 3)
+    if factor > 1:                                      # multiples of the factor: a common factor in practically every unit
+        img = (img.to(torch.int64) % min(2 ** (8 * tsz - 1) // factor, 4096) * factor).to(img.dtype)      # (4096 steps at most: no RLE0 win)
     raw = img.reshape(-1).view(torch.uint8)
-    enc = qdev.DeviceEncoder(w, h, b, dt, mode=8, want_index=False, index_chunk=2)
+    enc = qdev.DeviceEncoder(w, h, b, dt, mode=mode, want_index=False, index_chunk=2)
     dst, n, _ = enc.encode(raw)
     dec = qdev.DeviceDecoder(dst, n)
-    x0, y0 = 1001, 517
-    for side in (256, 1024, 4096):
-        out = torch.empty(side * side * b * tsz, dtype=torch.uint8, device="cuda")
-        crop = out.view(side, side * b * tsz)
-        want = raw.view(h, -1)[y0:y0 + side, x0 * b * tsz:(x0 + side) * b * tsz]
+    # (cfu: the last window is 2048^2 pixels as whole block rows, where the strips of path 2 decode nothing the window does not hold)
+    for x0, y0, side, wh in ((1001, 517, 256, 256), (1001, 517, 512, 512), (1001, 517, 2048, 2048), (0, 512, w, 512)) if cfu else \
+                            ((1001, 517, 256, 256), (1001, 517, 1024, 1024), (1001, 517, 4096, 4096)):
+        out = torch.empty(wh * side * b * tsz, dtype=torch.uint8, device="cuda")
+        crop = out.view(wh, side * b * tsz)
+        want = raw.view(h, -1)[y0:y0 + wh, x0 * b * tsz:(x0 + side) * b * tsz]
 
         def window():
-            dec.decode_window(dst, x0, y0, side, side, out=out)
+            dec.decode_window(dst, x0, y0, side, wh, out=out)
 
-        reps = 200 if side <= 1024 else 30
+        reps = 200 if side * wh <= 1024 * 1024 else 30
         t, last = {1: [], 0: []}, {}
         for _ in range(3):                              # alternating, three rounds each
             for on in (1, 0):
-                dec.set_window_kernels(QB3X_WINK_UNIT if on else 0)
+                dec.set_window_kernels(bit if on else 0)
                 out.zero_()
                 window()
                 assert torch.equal(crop, want), "window bytes"
@@ -156,17 +170,37 @@ def run_unit(case):
                 t[on].append(round(timed(window, reps), 4))
         kern = {}
         for on in (1, 0):
-            dec.set_window_kernels(QB3X_WINK_UNIT if on else 0)
+            dec.set_window_kernels(bit if on else 0)
             qdev.profile_reset()
             qdev.profile_enable(1)
             for _ in range(20):
                 window()
             torch.cuda.synchronize()
             qdev.profile_enable(0)
-            kern.update({k: round(v[0] / v[1], 4) for k, v in qdev.profile_report().items() if k in ("dec_window_unit", "dec_units")})
-        print(json.dumps({"case": case, "raster": [w, h, b], "bytes_per_value": tsz, "container_bytes": n, "window": [x0, y0, side, side],
+            kern.update({k: round(v[0] / v[1], 4) for k, v in qdev.profile_report().items() if k in (kname, "dec_units")})
+        batch = {}
+        if cfu and wh == side:                          # 64 windows of this side at seeded random origins, one call
+            rng = np.random.default_rng(side)
+            rects = [(int(rng.integers(1, w - side)), int(rng.integers(1, h - side)), side, side) for _ in range(64)]
+            outs = [torch.empty(side * side * b * tsz, dtype=torch.uint8, device="cuda") for _ in rects]
+            tb = {1: [], 0: []}
+            for _ in range(3):
+                for on in (1, 0):
+                    dec.set_window_kernels(bit if on else 0)
+                    dec.decode_windows(dst, rects, out=outs)
+                    for (bx, by, _, _), o in zip(rects[:2] + rects[-1:], outs[:2] + outs[-1:]):
+                        assert torch.equal(o.view(side, -1), raw.view(h, -1)[by:by + side, bx * b * tsz:(bx + side) * b * tsz]), "batch bytes"
+                    tb[on].append(round(timed(lambda: dec.decode_windows(dst, rects, out=outs), 10 if side <= 512 else 3), 4))
+            batch = {"batch": 64, "batch_ms": tb[1], "batch_off_ms": tb[0]}
+        print(json.dumps({"case": case, "mode": lib_mode(dec), **batch, "raster": [w, h, b], "bytes_per_value": tsz, "container_bytes": n, "window": [x0, y0, side, wh],
                           "path": last[1][0], "segments": last[1][1], "window_ms": t[1],
                           "path_off": last[0][0], "segments_off": last[0][1], "window_off_ms": t[0], "kernel_ms": kern}), flush=True)
+
+
+def lib_mode(dec):
+    """the container's mode byte (QB3M_BEST: 5 unless its RLE0 pass won)"""
+    from qb3_amd import lib
+    return lib.qb3_get_mode(dec.p)
 
 
 BATCH_CASES = {"batch256": (16384, 16384, 3, 2, 64, 256), "batch1024": (16384, 16384, 3, 2, 64, 1024), "batch_path3": (4096, 4096, 3, 0, 16, 256)}
@@ -322,9 +356,19 @@ def run_ranged(path, rect=None, kernels16=False, kernels_cf=False):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
-    k16, kcf, kunit = "--kernels16" in args, "--kernels-cf" in args, "--kernels-unit" in args
-    args = [a for a in args if a not in ("--kernels16", "--kernels-cf", "--kernels-unit")]
-    if kunit:
+    k16, kcf, kunit, kcfu = "--kernels16" in args, "--kernels-cf" in args, "--kernels-unit" in args, "--kernels-cfu" in args
+    args = [a for a in args if a not in ("--kernels16", "--kernels-cf", "--kernels-unit", "--kernels-cfu")]
+    if kcfu:
+        if args[:1] != ["best"] or (len(args) > 1 and args[1] not in CFU_CASES):
+            sys.exit("window_bench: --kernels-cfu goes with CASE best and, optionally, one of %s" % ", ".join(CFU_CASES))
+        if len(args) > 1:
+            run_unit(args[1], cfu=True)
+        else:
+            for shape in CFU_CASES:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "best", "--kernels-cfu", shape], timeout=300)
+                if r.returncode:
+                    sys.exit("window_bench: %s ended with status %d; nothing more is run" % (shape, r.returncode))
+    elif kunit:
         if args and args[0] not in UNIT_CASES:
             sys.exit("window_bench: --kernels-unit takes one of %s" % ", ".join(UNIT_CASES))
         if args:
