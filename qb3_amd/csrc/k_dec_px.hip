@@ -3,6 +3,13 @@
 
 namespace qb3dev {
 
+// loads from a table entry (entries are not dword aligned), and a 64-bit value that every lane of the wave loaded from the same address
+__device__ __forceinline__ uint32_t ld_u32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
+__device__ __forceinline__ uint32_t ld_u16(const uint8_t *p) { uint16_t v; __builtin_memcpy(&v, p, 2); return v; }
+__device__ __forceinline__ uint64_t uniform64(uint32_t lo, uint32_t hi) {
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)lo) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)hi) << 32;
+}
+
 // BL: no index -- the container's restart table has an entry per segment that ends with the bit lengths of the segment's
 // blocks (qb3x_set_encoder_index_chunk level 2): bit position, entering rungs and values come from the entry, a block's
 // place from the scan of the lengths, and a unit's place from where the band before it ended (the bands of a block are
@@ -17,7 +24,8 @@ __global__ void __launch_bounds__(256) dec_px_kernel(const DecArgs a0) {
         return;
     }
     constexpr int NW = (B + 1) / 2;                     // 32-bit words of a scan packed 16 bits per band
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));      // (a workgroup is 256 threads, four waves: launch_dec_px_b)
     const uint32_t NB = a.g.seg_blocks, nbx = a.g.nbx;  // NB <= 64: a WAVE owns a segment, nothing is shared but the table
     const uint64_t stride = a.g.stride;
 
@@ -25,66 +33,87 @@ __global__ void __launch_bounds__(256) dec_px_kernel(const DecArgs a0) {
     uint32_t *stage = tab + 1024 + wave * (a.in_cap_dw + 8);
     const uint32_t lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t *)smem;
     const uint32_t stage_bit0 = 8 * (lds0 + (uint32_t)((uint8_t *)stage - smem));
-    // Loads that depend on nothing but the segment number go out first -- positions, unit lengths, entering rungs and
-    // values -- so that their round trips overlap the table copy and its barrier (a wave spends 45 % of its life waiting
-    // for memory before it can start: the two dependent trips "position, then stream words").
-    const uint64_t seg = a.seg0 + (uint64_t)(blockIdx.x - chk) * nwaves + wave;       // (seg0, seg_end: this launch's range of segments)
+    // Two dependent round trips lie in front of the decoding, "entry, then stream words", and a wave spends a large part of its life
+    // in them.  The first is made of the loads that depend on nothing but the segment number: the thread's sixteen bytes of the code
+    // table, the position, the next segment's position, rungs and entering values, the lane's length(s).  All of them are
+    // unconditional -- where the condition is the lane's or the segment's there is a clamped address and a select behind the load --
+    // so they are issued back to back and waited for once; what they return is the same in every lane but the lengths, and goes to
+    // scalar registers.
+    const uint4 tabv = ((const uint4 *)px_dec_tab.e)[tid];
+    const uint64_t seg = a.seg0 + (uint64_t)(blockIdx.x - chk) * 4 + wave;             // (seg0, seg_end: this launch's range of segments)
     const bool live = seg < a.seg_end;
-    const uint64_t segc = live ? seg : 0;
+    const uint64_t segc = live ? seg : a.seg_end - 1;   // (a wave without a segment loads the launch's last one and drops it)
     const uint32_t g0 = (uint32_t)(segc * NB), nblocks = (uint32_t)a.g.nblocks;
     const uint32_t nb_here = (nblocks - g0 < NB) ? nblocks - g0 : NB;
     const bool act = live && lane < nb_here;
-    uint64_t P0, P1;
-    uint32_t ul_[B], rg0[B], pv0[B], blen = 0;
+    const uint32_t lc = lane < nb_here ? lane : nb_here - 1;       // a lane without a block loads the last block's length(s)
+    const bool last = segc + 1 >= a.g.nseg;              // behind the raster's last segment the stream ends: nothing to load
+    uint32_t p0lo, p0hi, p1lo, p1hi, hd0 = 0, hd1 = 0, len = 0, ulr[B], rgr[B], pvr[B];
     if (BL) {
-        const uint8_t *e = ix_entry_at(a.ix, a.ix_per_chunk, a.ix_E, a.ix_pad, (uint32_t)segc);
-        auto pos6 = [](const uint8_t *q) { uint64_t v = 0;
-#pragma unroll
-            for (uint32_t i = 0; i < 6; i++) v |= (uint64_t)q[i] << (8 * i);
-            return v; };
-        P0 = pos6(e);
-        P1 = (segc + 1 < a.g.nseg) ? pos6(ix_entry_at(a.ix, a.ix_per_chunk, a.ix_E, a.ix_pad, (uint32_t)segc + 1)) : a.in_bits;
-#pragma unroll
-        for (int c = 0; c < B; c++) { ul_[c] = 0; rg0[c] = e[6 + c] & 7u; pv0[c] = e[6 + B + c]; }
-        const uint8_t *bl = e + 6 + 2 * B + ((IX_BL_BITS * lane) >> 3);
-        blen = act ? (((uint32_t)bl[0] | (uint32_t)bl[1] << 8) >> ((IX_BL_BITS * lane) & 7)) & ((1u << IX_BL_BITS) - 1) : 0u;
+        // the entry and the one behind it (the first of the next chunk behind a chunk's last; layout: qb3_dev.h, IxTable), or the entry
+        // again; its fixed part in as few loads as its alignment allows: entries are not dword aligned
+        const uint32_t c = (uint32_t)segc / a.ix_per_chunk, j = (uint32_t)segc - c * a.ix_per_chunk;
+        const uint8_t *e = a.ix + (uint64_t)c * (IX_HEAD + a.ix_pad + (uint64_t)a.ix_per_chunk * a.ix_E) + IX_HEAD + (uint64_t)j * a.ix_E;
+        const uint8_t *en = last ? e : e + a.ix_E + (j + 1 == a.ix_per_chunk ? IX_HEAD + a.ix_pad : 0u);
+        p0lo = ld_u32(e); p0hi = ld_u16(e + 4);
+        p1lo = ld_u32(en); p1hi = ld_u16(en + 4);
+        if (B == 1) hd0 = ld_u16(e + 6);
+        else { hd0 = ld_u32(e + 6); hd1 = B == 3 ? ld_u16(e + 10) : ld_u32(e + 10); }
+        len = ld_u16(e + 6 + 2 * B + ((IX_BL_BITS * lc) >> 3));
     } else {
-        P0 = a.idx.bitpos[segc];
-        P1 = (segc + 1 < a.g.nseg) ? a.idx.bitpos[segc + 1] : a.in_bits;
-        if (P1 < P0) P1 = P0;       // (the last segment of a truncated stream starts behind its end: it reads zeros, like the reference's reader, bitstream.h:36)
-        const uint8_t *ul = (const uint8_t *)a.idx.ulen + ((uint64_t)g0 + lane) * B;
+        const uint64_t p0 = a.idx.bitpos[segc], p1 = a.idx.bitpos[last ? segc : segc + 1];
+        p0lo = (uint32_t)p0; p0hi = (uint32_t)(p0 >> 32); p1lo = (uint32_t)p1; p1hi = (uint32_t)(p1 >> 32);
+        const uint8_t *ul = (const uint8_t *)a.idx.ulen + ((uint64_t)g0 + lc) * B;
 #pragma unroll
         for (int c = 0; c < B; c++) {
-            ul_[c] = act ? ul[c] : 0u;
-            rg0[c] = a.idx.rung[segc * B + c];
-            pv0[c] = ((const uint8_t *)a.idx.prev)[segc * B + c];
+            ulr[c] = ul[c];
+            rgr[c] = a.idx.rung[segc * B + c];
+            pvr[c] = ((const uint8_t *)a.idx.prev)[segc * B + c];
         }
     }
-    for (uint32_t i = tid; i < 256; i += blockDim.x) ((uint4 *)tab)[i] = ((const uint4 *)px_dec_tab.e)[i];
+    ((uint4 *)tab)[tid] = tabv;
     __syncthreads();                                    // the only workgroup barrier
     if (!live) return;
+    const uint64_t P0 = uniform64(p0lo, p0hi);
+    uint64_t P1 = last ? a.in_bits : uniform64(p1lo, p1hi);
+    if (!BL && P1 < P0) P1 = P0;    // (the last segment of a truncated stream starts behind its end: it reads zeros, like the reference's reader, bitstream.h:36)
     const uint64_t w0 = (a.in_bit0 + P0) >> 5;
     const uint64_t endw_abs = (a.in_bit0 + a.in_bits + 31) >> 5;
     const uint64_t ndw64 = ((a.in_bit0 + P1 + 31) >> 5) - w0;
     // the staging area holds the longest valid segment; an index that says otherwise is not ours
     const bool fits = ndw64 <= a.in_cap_dw && lds0 == 0;
     const uint32_t ndw = fits ? (uint32_t)ndw64 : 0;
-    for (uint32_t base = 0; base < ndw + 8; base += 512) {          // eight loads in flight per lane, then eight LDS stores
-        uint32_t sw[8];
+    const uint64_t left = endw_abs > w0 ? endw_abs - w0 : 0;
+    const uint32_t lim = left < ndw ? (uint32_t)left : ndw;          // the words of them the stream has: the rest are staged as zeros
+    // Eight loads in flight per lane, then eight LDS stores, neither with a branch between them: a lane past the segment's words loads
+    // the last of them and stores a zero; 8 zero words follow the staged ones, and a lane past those stores the last zero again.  A
+    // segment without a word in the stream loads nothing (`lim` is the wave's: one jump round all eight).
+    for (uint32_t base = 0; base < ndw + 8; base += 512) {
+        uint32_t sw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (lim) {
+            const uint32_t *src = a.in32 + w0;
 #pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const uint32_t i = base + lane + 64 * k;
-            sw[k] = (i < ndw && w0 + i < endw_abs) ? a.in32[w0 + i] : 0u;
+            for (int k = 0; k < 8; k++) {
+                const uint32_t i = base + lane + 64 * k;
+                sw[k] = src[i < lim - 1 ? i : lim - 1];
+            }
         }
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             const uint32_t i = base + lane + 64 * k;
-            if (i < ndw + 8) stage[i] = sw[k];
+            stage[i < ndw + 7 ? i : ndw + 7] = i < lim ? sw[k] : 0u;
         }
     }
-    if (!BL)
+    uint32_t ul_[B], rg0[B], pv0[B], blen = 0;
+    if (BL) {
+        const uint64_t hd = uniform64(hd0, hd1);
 #pragma unroll
-        for (int c = 0; c < B; c++) blen += ul_[c];
+        for (int c = 0; c < B; c++) { ul_[c] = 0; rg0[c] = (uint32_t)(hd >> (8 * c)) & 7u; pv0[c] = (uint32_t)(hd >> (8 * (B + c))) & 0xffu; }
+        blen = act ? (len >> ((IX_BL_BITS * lc) & 7)) & ((1u << IX_BL_BITS) - 1) : 0u;
+    } else {
+#pragma unroll
+        for (int c = 0; c < B; c++) { ul_[c] = act ? ulr[c] : 0u; rg0[c] = rgr[c]; pv0[c] = pvr[c]; blen += ul_[c]; }
+    }
     // the wave reads what its own lanes staged: LDS operations of a wave execute in order, the fence is for the compiler
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
