@@ -1,9 +1,8 @@
 // qb3_amd/csrc/api_ranged.cpp -- ranged window reads (include/qb3x.h: qb3x_open_ranged, qb3x_read_windows_ranged,
 // qb3x_decode_windows_ranged): windows of a container that is read through a function of the caller's, fetching only the table chunks
 // and the pieces of the stream that hold the rectangles.  The rules of what is read are stated in qb3x.h; the kernels that decode from
-// the pieces are k_dec_wins_ranged.hip (8-bit rasters), k_dec_wins16_ranged.hip (16-bit ones, on a handle that asked: QB3X_WINK_U16) and
-// k_dec_wins_best_ranged.hip (8-bit rasters in the common-factor modes, on a handle that asked: QB3X_WINK_CF8); everything the shortcut
-// does not take goes, with the whole container, the way of api_window.cpp.
+// the pieces are the ranged form of the family that takes the raster (qb3_dev.h: window_family; a family without that form is no
+// shortcut here); everything the shortcut does not take goes, with the whole container, the way of api_window.cpp.
 #include <new>
 #include "qb3_host.h"
 
@@ -19,7 +18,6 @@ bool rg_read(decs *p, uint64_t off, void *dst, size_t n) {
     p->rg_reads++; p->rg_bytes += n;
     return p->rg_rd(p->rg_ctx, off, dst, n) == 0;
 }
-size_t rg_stride(const decs *p, const qb3x_window &w) { return w.dst_stride ? w.dst_stride : w.w * p->nbands; }
 uint64_t pos6(const uint8_t *q) {
     uint64_t v = 0;
     for (uint32_t i = 0; i < 6; i++) v |= (uint64_t)q[i] << (8 * i);
@@ -35,37 +33,22 @@ struct Chunks {
     size_t size(uint32_t c) const { return IX_HEAD + (size_t)entries(c) * E + IX_PAD + (c + 1 == count ? 2 : 0); }
 };
 
-// does the shortcut take this handle's raster and table, and with which kernels (pure: no device, no reader)
-enum class Shortcut { none, u8, u16, cf8 };
-Shortcut ranged_shortcut(const decs *p, Geometry &g, DecPlan &plan, IxTable &ixt, Chunks &ch) {
-    if (p->mode == QB3M_STORED || p->xsize < 4 || p->ysize < 4 || !p->ix_K || !p->ix_bl || p->ix_ver < 3 || !p->ix_pads || is_rle_mode(p->mode)) return Shortcut::none;
+// does the shortcut take this handle's raster and table, and with which family's kernels (pure: no device, no reader); null: no
+const WinKernels *ranged_shortcut(const decs *p, Geometry &g, DecPlan &plan, IxTable &ixt, Chunks &ch) {
+    if (p->mode == QB3M_STORED || p->xsize < 4 || p->ysize < 4 || !p->ix_K || !p->ix_bl || p->ix_ver < 3 || !p->ix_pads || is_rle_mode(p->mode)) return nullptr;
     g = decoder_geometry(p, p->xsize, p->ysize, 0);
     plan = plan_decode(g);
     ixt = handle_table(p, (const uint8_t *)p);          // (the table is not in device memory: the base only has to be non-null)
-    const Shortcut family = decode_window_ok(g, plan, ixt) ? Shortcut::u8
-                          : (p->win_kernels & QB3X_WINK_U16) && decode_window16_ok(g, plan, ixt) ? Shortcut::u16
-                          : (p->win_kernels & QB3X_WINK_CF8) && decode_window_best_ok(g, plan, ixt) ? Shortcut::cf8 : Shortcut::none;
-    if (family == Shortcut::none) return family;
+    const WinKernels *family = window_family(g, plan, ixt, p->win_kernels);
+    if (!family || !family->ranged) return nullptr;
     ch.off = p->ix_off; ch.K = p->ix_K; ch.N = p->ix_per_chunk; ch.E = p->ix_E; ch.count = (uint32_t)ix_chunks(ixt);
-    return ch.at(ch.count - 1) + ch.size(ch.count - 1) <= p->rg_size ? family : Shortcut::none;
+    return ch.at(ch.count - 1) + ch.size(ch.count - 1) <= p->rg_size ? family : nullptr;
 }
 
-struct BlockRect { uint32_t bx0, bx1, by0, by1; };
-BlockRect block_rect(const Geometry &g, const qb3x_window &w) {
-    return BlockRect{ std::min((uint32_t)(w.x0 / 4), g.nbx - 1), std::min((uint32_t)((w.x0 + w.w - 1) / 4), g.nbx - 1),
-                      std::min((uint32_t)(w.y0 / 4), g.nby - 1), std::min((uint32_t)((w.y0 + w.h - 1) / 4), g.nby - 1) };
-}
-// table chunks an entry of a window is read from: the first segment's to the one of the entry behind the last segment; and the last
-void chunk_list(const Geometry &g, const Chunks &ch, const qb3x_window *wins, size_t n, std::vector<uint32_t> &chunks) {
-    chunks.clear();
-    for (size_t i = 0; i < n; i++) {
-        const BlockRect b = block_rect(g, wins[i]);
-        const uint64_t first = ((uint64_t)b.by0 * g.nbx + b.bx0) / g.seg_blocks, last = std::min<uint64_t>(((uint64_t)b.by1 * g.nbx + b.bx1) / g.seg_blocks + 1, ch.K - 1);
-        for (uint64_t c = first / ch.N; c <= last / ch.N; c++) chunks.push_back((uint32_t)c);
-    }
-    chunks.push_back((ch.K - 1) / ch.N);
-    std::sort(chunks.begin(), chunks.end());
-    chunks.erase(std::unique(chunks.begin(), chunks.end()), chunks.end());
+std::vector<WinRect> window_rects(const qb3x_window *wins, size_t n) {      // (strides: filled where they matter)
+    std::vector<WinRect> rects(n);
+    for (size_t i = 0; i < n; i++) rects[i] = WinRect{ (uint32_t)wins[i].x0, (uint32_t)wins[i].y0, (uint32_t)wins[i].w, (uint32_t)wins[i].h, 0 };
+    return rects;
 }
 
 // The host twin of ix_check_chunk (qb3_kernels.h): head (flag bit 0: common-factor entries; bit 1: block fields, which the shortcut
@@ -109,11 +92,6 @@ void trim_cache(decs *p) {
 
 struct Piece { uint32_t seg0, nseg, ent0, word0, sw0_lo, sw0_hi, nwords, pad_; };      // WinPiece of qb3_win.h, as uploaded
 static_assert(sizeof(Piece) == WIN_PIECE_BYTES, "the piece list is uploaded as it is");
-// the kernels the shortcut goes through, by their launchers
-int (*const ranged_launchers[])(const Geometry &, const DecPlan &, uint32_t, uint64_t, const void *, const void *, size_t, const void *, size_t, const void *,
-                                const uint32_t *, uint32_t *, void *, const IxTable &) = {      // in Shortcut's order
-    nullptr, launch_decode_windows_ranged, launch_decode_windows16_ranged, launch_decode_windows_best_ranged };
-
 // The whole container through the reader, once, and the windows the way of qb3x_read_windows / qb3x_decode_windows_device
 size_t whole_container(decsp p, const qb3x_window *wins, size_t n, uint8_t *paths, bool host, hipStream_t st) {
     const size_t csize = (size_t)p->rg_size, off = (size_t)(p->s_in - p->s_start);
@@ -143,7 +121,7 @@ size_t stored_windows(decsp p, const qb3x_window *wins, size_t n, uint8_t *paths
     std::vector<uint8_t> tmp;
     for (size_t i = 0; i < n; i++) {
         const qb3x_window &w = wins[i];
-        const size_t wline = w.w * pix, dline = host ? rg_stride(p, w) * tsz : wline;
+        const size_t wline = w.w * pix, dline = host ? win_stride(p, w) * tsz : wline;
         uint8_t *to = (uint8_t *)w.dst;
         if (!host) { tmp.resize(w.h * wline); to = tmp.data(); }
         bool ok;
@@ -154,7 +132,7 @@ size_t stored_windows(decsp p, const qb3x_window *wins, size_t n, uint8_t *paths
         }
         if (!ok) { p->error = QB3E_ERR; return 0; }
         if (!host) {
-            if (hipMemcpy2DAsync(w.dst, rg_stride(p, w) * tsz, to, wline, wline, w.h, hipMemcpyHostToDevice, st) != hipSuccess ||
+            if (hipMemcpy2DAsync(w.dst, win_stride(p, w) * tsz, to, wline, wline, w.h, hipMemcpyHostToDevice, st) != hipSuccess ||
                 hipStreamSynchronize(st) != hipSuccess) { p->error = QB3E_LIBERR; return 0; }
         }
         paths[i] = 3;
@@ -165,18 +143,19 @@ size_t stored_windows(decsp p, const qb3x_window *wins, size_t n, uint8_t *paths
 
 // The shortcut.  Marks the windows it gave their pixels (paths[i] = 1) and counts their segments.  1: went through (fall back for the
 // windows that are left); 0: the table is not to be trusted, nothing was written; -1: the call failed (p->error is set).  family:
-// whose kernels -- a 16-bit raster (Shortcut::u16) has its own blocks per segment (g.seg_blocks) and value size, a common-factor one
-// (Shortcut::cf8) its own entries (ch.E) and head flags; all else is one code
+// whose kernels -- a raster has its own blocks per segment (g.seg_blocks) and value size, a common-factor one its own entries (ch.E)
+// and head flags; all else is one code
 int pieces_windows(decsp p, const Geometry &g, const DecPlan &plan, const IxTable &ixt, const Chunks &ch, const qb3x_window *wins, size_t n,
-                   uint8_t *paths, size_t *segs, bool host, hipStream_t st, Shortcut family) {
+                   uint8_t *paths, size_t *segs, bool host, hipStream_t st, const WinKernels &family) {
     const size_t tsz = szof(p->type), pix = p->nbands * tsz;
     const uint64_t csize = p->rg_size, off = (uint64_t)(p->s_in - p->s_start), base = off & ~(uint64_t)3, in_bits = (uint64_t)p->s_size * 8;
     const uint32_t in_bit0 = (uint32_t)(8 * (off & 3));
     // stage 1: the table chunks the windows' entries are in
     std::vector<uint32_t> chunks;
     std::vector<const uint8_t *> cdata;
-    chunk_list(g, ch, wins, n, chunks);
-    const int got = fetch_chunks(p, ch, chunks, cdata, family == Shortcut::cf8 ? 3u : 2u);
+    std::vector<WinRect> rects = window_rects(wins, n);
+    window_chunk_list(g, ch.K, ch.N, rects.data(), n, chunks);
+    const int got = fetch_chunks(p, ch, chunks, cdata, g.mode == CM_BEST ? 3u : 2u);
     if (got == 2) { p->error = QB3E_ERR; return -1; }
     if (got) return 0;
     auto entry = [&](uint32_t k) -> const uint8_t * {
@@ -188,22 +167,16 @@ int pieces_windows(decsp p, const Geometry &g, const DecPlan &plan, const IxTabl
     // stage 2: runs of segments, one per block row of a window; merged where they overlap or follow each other
     std::vector<std::pair<uint32_t, uint32_t>> runs;    // [first, end)
     for (size_t i = 0; i < n; i++) {
-        const BlockRect b = block_rect(g, wins[i]);
+        const WinBlocks b = window_blocks(g, wins[i].x0, wins[i].y0, wins[i].w, wins[i].h);
         for (uint64_t by = b.by0; by <= b.by1; by++) runs.emplace_back((uint32_t)((by * g.nbx + b.bx0) / g.seg_blocks), (uint32_t)((by * g.nbx + b.bx1) / g.seg_blocks + 1));
     }
-    std::sort(runs.begin(), runs.end());
-    size_t m = 0;
-    for (size_t i = 1; i < runs.size(); i++) {
-        if (runs[i].first <= runs[m].second) runs[m].second = std::max(runs[m].second, runs[i].second);
-        else runs[++m] = runs[i];
-    }
-    runs.resize(m + 1);
+    merge_ranges(runs);
     // a piece per run whose two ends make sense: inside the stream, no longer than its segments can be (px_cap_dw: the worst-case
     // segment of every family; a table that says otherwise is not this stream's; the waves of such a run find no piece and raise
     // their window's status)
-    struct Span { uint64_t a, b; size_t at; };         // container bytes [a, b); at: where they start in the packed words (bytes)
     std::vector<Piece> pieces;
-    std::vector<Span> spans;
+    std::vector<std::pair<uint64_t, uint64_t>> spans;  // container bytes [first, second) ...
+    std::vector<size_t> span_at;                        // ... and where they start in the packed words (bytes)
     std::vector<uint64_t> piece_a;
     size_t nents = 0;
     for (const auto &r : runs) {
@@ -216,38 +189,26 @@ int pieces_windows(decsp p, const Geometry &g, const DecPlan &plan, const IxTabl
         const uint64_t a = std::min(base + 4 * w0, csize), b = std::min(base + 4 * w1, csize);
         pieces.push_back(pc);
         piece_a.push_back(a);
-        if (b > a) spans.push_back(Span{ a, b, 0 });
+        if (b > a) spans.emplace_back(a, b);
     }
     if (pieces.empty() || nents > 0x7fffffffull) return 0;
-    std::sort(spans.begin(), spans.end(), [](const Span &x, const Span &y) { return x.a < y.a; });
-    m = 0;
-    for (size_t i = 1; i < spans.size(); i++) {        // merged where they overlap, touch or lie within the gap
-        if (spans[i].a - std::min(spans[i].a, spans[m].b) <= p->rg_gap) spans[m].b = std::max(spans[m].b, spans[i].b);
-        else spans[++m] = spans[i];
-    }
-    if (!spans.empty()) spans.resize(m + 1);
+    merge_ranges(spans, (uint64_t)p->rg_gap);
     uint64_t wbytes = 0;
-    for (auto &s : spans) { s.at = (size_t)wbytes; wbytes += (s.b - s.a + 3) & ~(uint64_t)3; }
+    for (const auto &s : spans) { span_at.push_back((size_t)wbytes); wbytes += (s.second - s.first + 3) & ~(uint64_t)3; }
     if (wbytes >= ((uint64_t)1 << 32)) return 0;
     // what goes up, in one pinned area: descriptors, piece list, entries, words
     const size_t dbytes = n * WIN_DESC_BYTES, pbytes = pieces.size() * sizeof(Piece), ebytes = (nents * ch.E + 15) & ~(size_t)15;
     const size_t upbytes = dbytes + pbytes + ebytes + (size_t)wbytes + 4, stbytes = 4 * (n + 1);
     if (!device_ok()) { p->error = QB3E_LIBERR; return -1; }
-    size_t obytes = 0;
-    if (host) for (size_t i = 0; i < n; i++) obytes += (wins[i].h * wins[i].w * pix + 3) & ~(size_t)3;
-    if (!p->h_rg.ensure(upbytes) || !p->d_rg.ensure(upbytes) || !p->h_wst.ensure(stbytes) || !p->d_wst.ensure(stbytes) || (host && !p->d_wout.ensure(obytes))) {
+    std::vector<void *> dsts(n);
+    if (!p->h_rg.ensure(upbytes) || !p->d_rg.ensure(upbytes) || !p->h_wst.ensure(stbytes) || !p->d_wst.ensure(stbytes) || (host && !windows_out(p, wins, n, dsts))) {
         p->error = QB3E_LIBERR;
         return -1;
     }
     uint8_t *up = (uint8_t *)p->h_rg.p, *h_words = up + dbytes + pbytes + ebytes;
-    std::vector<WinRect> rects(n);
-    std::vector<void *> dsts(n);
-    obytes = 0;
     for (size_t i = 0; i < n; i++) {
-        const qb3x_window &w = wins[i];
-        rects[i] = WinRect{ (uint32_t)w.x0, (uint32_t)w.y0, (uint32_t)w.w, (uint32_t)w.h, host ? w.w * p->nbands : rg_stride(p, w) };
-        dsts[i] = host ? (void *)((uint8_t *)p->d_wout.p + obytes) : w.dst;
-        obytes += (w.h * w.w * pix + 3) & ~(size_t)3;
+        rects[i].stride = host ? wins[i].w * p->nbands : win_stride(p, wins[i]);
+        if (!host) dsts[i] = wins[i].dst;
     }
     std::vector<uint32_t> unused;
     uint64_t wsegs = 0;
@@ -260,19 +221,19 @@ int pieces_windows(decsp p, const Geometry &g, const DecPlan &plan, const IxTabl
             else memset(e, 0, ch.E);                    // (behind the raster's last segment: the stream's length ends it)
         }
         size_t lo = 0, hi = spans.size();
-        while (hi - lo > 1) { const size_t mid = (lo + hi) / 2; if (spans[mid].a <= piece_a[k]) lo = mid; else hi = mid; }
+        while (hi - lo > 1) { const size_t mid = (lo + hi) / 2; if (spans[mid].first <= piece_a[k]) lo = mid; else hi = mid; }
         uint64_t avail = 0;
-        if (!spans.empty() && spans[lo].a <= piece_a[k]) {
-            const uint64_t rel = piece_a[k] - spans[lo].a, room = (spans[lo].b - spans[lo].a + 3) & ~(uint64_t)3;
-            if (rel <= room) { pc.word0 = (uint32_t)((spans[lo].at + rel) / 4); avail = (room - rel) / 4; }
+        if (!spans.empty() && spans[lo].first <= piece_a[k]) {
+            const uint64_t rel = piece_a[k] - spans[lo].first, room = (spans[lo].second - spans[lo].first + 3) & ~(uint64_t)3;
+            if (rel <= room) { pc.word0 = (uint32_t)((span_at[lo] + rel) / 4); avail = (room - rel) / 4; }
         }
         pc.nwords = (uint32_t)std::min<uint64_t>(pc.nwords, avail);        // never a word outside what was packed
     }
     memcpy(up + dbytes, pieces.data(), pbytes);
-    for (const auto &s : spans) {
-        const size_t len = (size_t)(s.b - s.a);
-        if (!rg_read(p, s.a, h_words + s.at, len)) { p->error = QB3E_ERR; return -1; }
-        memset(h_words + s.at + len, 0, (0 - len) & 3);
+    for (size_t k = 0; k < spans.size(); k++) {
+        const size_t len = (size_t)(spans[k].second - spans[k].first);
+        if (!rg_read(p, spans[k].first, h_words + span_at[k], len)) { p->error = QB3E_ERR; return -1; }
+        memset(h_words + span_at[k] + len, 0, (0 - len) & 3);
     }
     // one copy up, one launch, the status words back
     uint32_t *d_status = (uint32_t *)p->d_wst.p;
@@ -281,7 +242,7 @@ int pieces_windows(decsp p, const Geometry &g, const DecPlan &plan, const IxTabl
     hipError_t e = hipMemcpyAsync(p->d_rg.p, up, upbytes - 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_status, 0, stbytes, st);
     if (e != hipSuccess) return hip_fail("ranged windows: upload", e);
-    if (ranged_launchers[(int)family](g, plan, in_bit0, in_bits, up, d_up, n, d_up + dbytes, pieces.size(), d_up + dbytes + pbytes,
+    if (launch_decode_windows_ranged(family, g, plan, in_bit0, in_bits, up, d_up, n, d_up + dbytes, pieces.size(), d_up + dbytes + pbytes,
                                      (const uint32_t *)(d_up + dbytes + pbytes + ebytes), d_status, st, ixt)) return hip_fail("ranged windows: launch", hipSuccess);
     e = hipMemcpyAsync(p->h_wst.p, d_status, stbytes, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = wait_stream(st);
@@ -291,12 +252,10 @@ int pieces_windows(decsp p, const Geometry &g, const DecPlan &plan, const IxTabl
     for (size_t i = 0; i < n; i++) {
         if (status[1 + i]) continue;
         paths[i] = 1;
-        Geometry gw = g;                                // the window as a raster of its own: what is dequantised
-        gw.w = rects[i].w; gw.h = rects[i].h; gw.stride = rects[i].stride;
-        if (p->quanta > 1 && launch_dequantize(dsts[i], gw, (int)p->type, p->quanta, st)) return hip_fail("ranged windows: dequantize", hipSuccess);
+        if (!window_dequantize(p, g, dsts[i], rects[i].w, rects[i].h, rects[i].stride, st)) return hip_fail("ranged windows: dequantize", hipSuccess);
         if (host) {
             const size_t wline = wins[i].w * pix;
-            e = hipMemcpy2DAsync(wins[i].dst, rg_stride(p, wins[i]) * tsz, dsts[i], wline, wline, wins[i].h, hipMemcpyDeviceToHost, st);
+            e = hipMemcpy2DAsync(wins[i].dst, win_stride(p, wins[i]) * tsz, dsts[i], wline, wline, wins[i].h, hipMemcpyDeviceToHost, st);
             if (e != hipSuccess) return hip_fail("ranged windows: download", e);
         }
     }
@@ -318,12 +277,11 @@ size_t ranged_call(decsp p, const qb3x_window *wins, size_t n, bool host, hipStr
     IxTable ixt;
     Chunks ch;
     size_t segs = 0;
-    Shortcut family = ranged_shortcut(p, g, plan, ixt, ch);
-    // the 16-bit kernels store halfwords: one device destination on an odd address and the call goes windows_device's way, which
+    // a family that stores halfwords or values: one device destination off its alignment and the call goes windows_device's way, which
     // applies the same test (host destinations are decoded into the handle's buffer, every window on a dword)
-    for (size_t i = 0; family == Shortcut::u16 && !host && i < n; i++) if ((uintptr_t)wins[i].dst & 1) family = Shortcut::none;
-    if (family != Shortcut::none) {
-        const int went = pieces_windows(p, g, plan, ixt, ch, wins, n, paths, &segs, host, st, family);
+    const WinKernels *family = family_if_aligned(ranged_shortcut(p, g, plan, ixt, ch), g, wins, host ? 0 : n);
+    if (family) {
+        const int went = pieces_windows(p, g, plan, ixt, ch, wins, n, paths, &segs, host, st, *family);
         trim_cache(p);
         if (went < 0) return 0;
     }
@@ -432,15 +390,15 @@ QB3_API size_t qb3x_ranged_table_ranges(const decsp p, const qb3x_window *wins, 
     return abi_guard<size_t>(0, [&]() -> size_t {
         for (size_t i = 0; i < n; i++) {
             const qb3x_window &w = wins[i];
-            if (!(w.w && w.h && w.x0 < p->xsize && w.w <= p->xsize - w.x0 && w.y0 < p->ysize && w.h <= p->ysize - w.y0)) return 0;
+            if (!window_inside(p, w.x0, w.y0, w.w, w.h)) return 0;
         }
         Geometry g;
         DecPlan plan;
         IxTable ixt;
         Chunks ch;
-        if (ranged_shortcut(p, g, plan, ixt, ch) == Shortcut::none) return 0;
+        if (!ranged_shortcut(p, g, plan, ixt, ch)) return 0;
         std::vector<uint32_t> chunks;
-        chunk_list(g, ch, wins, n, chunks);
+        window_chunk_list(g, ch.K, ch.N, window_rects(wins, n).data(), n, chunks);
         for (size_t i = 0; out && i < chunks.size() && i < cap; i++) out[i] = qb3x_range{ ch.at(chunks[i]), ch.size(chunks[i]) };
         return chunks.size();
     });

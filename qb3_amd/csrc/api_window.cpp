@@ -8,25 +8,18 @@ using namespace qb3api;
 
 // A window's bytes are by definition "decode everything, crop" (path 3); the other two ways are shortcuts to the same bytes that are
 // taken when the container carries a level-2 table and dropped again on ANY nonzero status word:
-//   path 1  8-bit rasters of 1, 3 or 4 bands, FTL / BASE: a window kernel decodes only the segments that hold a block of a window,
-//           straight into the caller's buffer.  The single call's kernel (k_dec_win.hip) takes its window as kernel arguments and
-//           gives one status word; the batch's (k_dec_wins.hip) decodes all windows in ONE launch, a status word per window.
-//           On a handle that asked for them (qb3x_set_decoder_window_kernels, QB3X_WINK_U16) also 16-bit rasters of 1, 2, 3, 4, 6 or
-//           8 bands, through the kernels of k_dec_win16.hip, and (QB3X_WINK_CF8) 8-bit rasters of 1, 3 or 4 bands in the common-factor
-//           modes, through those of k_dec_win_best.hip, and (QB3X_WINK_UNIT) the FTL / BASE rasters of the lane-per-unit decoder and
-//           one-band 32/64-bit rasters, through those of k_dec_win_unit.hip, and (QB3X_WINK_CFU) the common-factor streams of such shapes and
-//           of one-band 16-bit rasters, through those of k_dec_win_best_unit.hip (WinFamily: what the two functions below pick their launcher by);
+//   path 1  a raster one of the families of window kernels takes (window_family, qb3_dev.h: 8-bit rasters of 1, 3 or 4 bands in FTL /
+//           BASE always; the other four on a handle that asked for them, qb3x_set_decoder_window_kernels) and destinations aligned as
+//           the family stores: a window kernel decodes only the segments that hold a block of a window, straight into the caller's
+//           buffer.  The single call's kernel takes its window as kernel arguments and gives one status word; the batch's decodes
+//           all windows in ONE launch, a status word per window;
 //   path 2  every other raster that decodes strip by strip (decode_strips_ok): the windows' block rows as ranges of segments, merged
 //           so that a segment is decoded once, into the handle's scratch raster, then a crop per window;
 //   path 3  ONE whole decode with its fallback ladder into the scratch raster for all windows that have no pixels yet, then their crops.
 // Everything but path 1 is written once, over a span of windows.  The single calls pass a span of one and a result word of their
 // own, so the per-window results of an earlier batch (qb3x_window_ok / qb3x_window_path) stay as they are.
 
-static size_t win_stride(const decs *p, const qb3x_window &w) { return w.dst_stride ? w.dst_stride : w.w * p->nbands; }    // values between the destination's rows
 static WinRect win_rect(const decs *p, const qb3x_window &w) { return WinRect{ (uint32_t)w.x0, (uint32_t)w.y0, (uint32_t)w.w, (uint32_t)w.h, win_stride(p, w) }; }
-static bool window_inside(const decs *p, size_t x0, size_t y0, size_t w, size_t h) {
-    return w && h && x0 < p->xsize && w <= p->xsize - x0 && y0 < p->ysize && h <= p->ysize - y0;
-}
 static bool window_check(const decs *p, const qb3x_window &w) {
     return w.dst && window_inside(p, w.x0, w.y0, w.w, w.h) && (!w.dst_stride || w.dst_stride >= w.w * p->nbands);
 }
@@ -59,22 +52,12 @@ static WinSrc window_source(const decs *p, const Geometry &g, const void *d_src)
                    (uint32_t)(8 * (off & 3)), (uint64_t)p->s_size * 8 };
 }
 
-// the kernels path 1 goes through, and their launchers: the single call's and the batch's
-enum class WinFamily { none, u8, u16, cf8, unit, cfu };
-static const struct {
-    int (*one)(const Geometry &, const DecPlan &, const uint32_t *, uint32_t, uint64_t, void *, const WinRect &, uint32_t *, void *, const IxTable &);
-    int (*batch)(const Geometry &, const DecPlan &, const uint32_t *, uint32_t, uint64_t, const void *, const void *, size_t, const uint32_t *, size_t, uint32_t *, void *, const IxTable &);
-} win_launchers[] = {      // in WinFamily's order
-    { nullptr, nullptr }, { launch_decode_window, launch_decode_windows }, { launch_decode_window16, launch_decode_windows16 },
-    { launch_decode_window_best, launch_decode_windows_best }, { launch_decode_window_unit, launch_decode_windows_unit },
-    { launch_decode_window_best_unit, launch_decode_windows_best_unit } };
-
 // The three functions below mark the windows they gave their pixels (paths[i]) and count the segments they decoded; false: a HIP failure.
 // path 1, the single call: the window as kernel arguments, one status word back
-static bool window_kernel_one(decsp p, const WinSrc &s, const qb3x_window &w, uint8_t *path, size_t *segs, hipStream_t st, WinFamily fam) {
+static bool window_kernel_one(decsp p, const WinSrc &s, const qb3x_window &w, uint8_t *path, size_t *segs, hipStream_t st, const WinKernels &fam) {
     const WinRect r = win_rect(p, w);
     uint32_t status = 1;
-    if (!p->d_wst.ensure(64) || win_launchers[(int)fam].one(s.g, s.plan, s.in32, s.in_bit0, s.in_bits, w.dst, r, (uint32_t *)p->d_wst.p, st, s.ixt)) return false;
+    if (!p->d_wst.ensure(64) || launch_decode_window(fam, s.g, s.plan, s.in32, s.in_bit0, s.in_bits, w.dst, r, (uint32_t *)p->d_wst.p, st, s.ixt)) return false;
     const hipError_t e = fetch_small(&status, p->d_wst.p, 4, st);
     if (e != hipSuccess) { set_error("window kernel", (int)e); return false; }
     *segs = (size_t)window_segments(s.g, r);
@@ -82,7 +65,7 @@ static bool window_kernel_one(decsp p, const WinSrc &s, const qb3x_window &w, ui
     return true;
 }
 // path 1, a batch: descriptors and the chunk list are built in the pinned area, one copy up; n + 1 status words, one memset, one copy back
-static bool window_kernel_batch(decsp p, const WinSrc &s, const qb3x_window *wins, size_t n, uint8_t *paths, size_t *segs, hipStream_t st, WinFamily fam) {
+static bool window_kernel_batch(decsp p, const WinSrc &s, const qb3x_window *wins, size_t n, uint8_t *paths, size_t *segs, hipStream_t st, const WinKernels &fam) {
     const size_t dbytes = n * WIN_DESC_BYTES, upbytes = dbytes + 4 * ix_chunks(s.ixt), stbytes = 4 * (n + 1);
     if (!p->h_wdesc.ensure(upbytes) || !p->h_wst.ensure(stbytes) || !p->d_wdesc.ensure(upbytes) || !p->d_wst.ensure(stbytes)) return false;
     std::vector<WinRect> rects(n);
@@ -95,7 +78,7 @@ static bool window_kernel_batch(decsp p, const WinSrc &s, const qb3x_window *win
     uint32_t *d_status = (uint32_t *)p->d_wst.p;
     HIPOK(hipMemcpyAsync(p->d_wdesc.p, p->h_wdesc.p, dbytes + 4 * nchunks, hipMemcpyHostToDevice, st));
     if (hipMemsetAsync(d_status, 0, stbytes, st) != hipSuccess) return false;
-    if (win_launchers[(int)fam].batch(s.g, s.plan, s.in32, s.in_bit0, s.in_bits, p->h_wdesc.p, p->d_wdesc.p, n,
+    if (launch_decode_windows(fam, s.g, s.plan, s.in32, s.in_bit0, s.in_bits, p->h_wdesc.p, p->d_wdesc.p, n,
                               (const uint32_t *)((const uint8_t *)p->d_wdesc.p + dbytes), nchunks, d_status, st, s.ixt)) return false;
     hipError_t e = hipMemcpyAsync(p->h_wst.p, d_status, stbytes, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = wait_stream(st);
@@ -112,17 +95,12 @@ static bool window_strips(decsp p, const WinSrc &s, const qb3x_window *wins, siz
     if (!p->d_win.ensure(qb3_decoded_size(p)) || !p->d_ws.ensure(s.plan.ws_bytes)) return false;
     std::vector<std::pair<uint64_t, uint64_t>> rg(n);
     for (size_t i = 0; i < n; i++) {
-        const uint64_t by0 = std::min<uint64_t>(wins[i].y0 / 4, g.nby - 1), by1 = std::min<uint64_t>((wins[i].y0 + wins[i].h - 1) / 4, g.nby - 1);
-        rg[i] = { by0 * g.nbx / g.seg_blocks, ((by1 + 1) * g.nbx - 1) / g.seg_blocks + 1 };
+        const WinBlocks b = window_blocks(g, wins[i].x0, wins[i].y0, wins[i].w, wins[i].h);
+        rg[i] = { (uint64_t)b.by0 * g.nbx / g.seg_blocks, ((uint64_t)(b.by1 + 1) * g.nbx - 1) / g.seg_blocks + 1 };
     }
-    std::sort(rg.begin(), rg.end());
-    size_t m = 0;
-    for (size_t i = 1; i < n; i++) {
-        if (rg[i].first <= rg[m].second) rg[m].second = std::max(rg[m].second, rg[i].second);
-        else rg[++m] = rg[i];
-    }
+    merge_ranges(rg);
     uint32_t *d_status = nullptr, status = 1;
-    for (size_t k = 0; k <= m; k++) {               // the first with first-strip semantics: status zeroed, table checked
+    for (size_t k = 0; k < rg.size(); k++) {               // the first with first-strip semantics: status zeroed, table checked
         const DecStrip strip = { rg[k].first, rg[k].second - rg[k].first, k == 0 };
         if (launch_decode(g, s.plan, s.in32, s.in_bit0, s.in_bits, p->d_win.p, nullptr, p->d_ws.p, &d_status, st, TileBatch(), nullptr, s.ixt,
                           nullptr, 0, false, 16, &strip)) return false;
@@ -152,29 +130,16 @@ size_t qb3api::windows_device(decsp p, const void *d_src, const void *d_index, c
         if (!device_ok()) { p->error = QB3E_LIBERR; return 0; }
         const WinSrc s = window_source(p, g, d_src);
         bool scratch = false;
-        // the 16-bit window kernels: a handle that asked, a raster and table they take, halfword stores to every destination
-        bool wide = (p->win_kernels & QB3X_WINK_U16) && decode_window16_ok(g, s.plan, s.ixt);
-        for (size_t i = 0; wide && i < n; i++) wide = ((uintptr_t)wins[i].dst & 1) == 0;
-        // the lane-per-unit window kernels: a handle that asked, a raster and table they take, value-aligned stores to every destination
-        bool unit = (p->win_kernels & QB3X_WINK_UNIT) && decode_window_unit_ok(g, s.plan, s.ixt);
-        for (size_t i = 0; unit && i < n; i++) unit = ((uintptr_t)wins[i].dst & (g.tsz - 1)) == 0;
-        // ... and those of the common-factor streams of such shapes: the same
-        bool cfu = (p->win_kernels & QB3X_WINK_CFU) && decode_window_best_unit_ok(g, s.plan, s.ixt);
-        for (size_t i = 0; cfu && i < n; i++) cfu = ((uintptr_t)wins[i].dst & (g.tsz - 1)) == 0;
-        // the 8-bit common-factor window kernels: a handle that asked, a raster and table they take; byte stores, any destination
-        const WinFamily fam = wide ? WinFamily::u16 : decode_window_ok(g, s.plan, s.ixt) ? WinFamily::u8
-                            : (p->win_kernels & QB3X_WINK_CF8) && decode_window_best_ok(g, s.plan, s.ixt) ? WinFamily::cf8
-                            : unit ? WinFamily::unit : cfu ? WinFamily::cfu : WinFamily::none;
-        if (fam != WinFamily::none) {
-            if (!(single ? window_kernel_one(p, s, wins[0], paths, &segs, st, fam) : window_kernel_batch(p, s, wins, n, paths, &segs, st, fam))) return fail();
+        // path 1: the family that takes the raster and its table, on a handle that asked for it, with stores every destination is aligned for
+        const WinKernels *fam = family_if_aligned(window_family(g, s.plan, s.ixt, p->win_kernels), g, wins, n);
+        if (fam) {
+            if (!(single ? window_kernel_one(p, s, wins[0], paths, &segs, st, *fam) : window_kernel_batch(p, s, wins, n, paths, &segs, st, *fam))) return fail();
         } else if ((scratch = decode_strips_ok(g, s.plan, s.ixt))) {
             if (!window_strips(p, s, wins, n, paths, &segs, st)) return fail();
         }
         for (size_t i = 0; i < n; i++) {
             if (!paths[i]) continue;
-            Geometry gw = g;                                // the window as a raster of its own: what is dequantised
-            gw.w = (uint32_t)wins[i].w; gw.h = (uint32_t)wins[i].h; gw.stride = win_stride(p, wins[i]);
-            if (p->quanta > 1 && launch_dequantize(wins[i].dst, gw, (int)p->type, p->quanta, st)) return fail();
+            if (!window_dequantize(p, g, wins[i].dst, wins[i].w, wins[i].h, win_stride(p, wins[i]), st)) return fail();
             todo--;
         }
         if (scratch && !todo && hipStreamSynchronize(st) != hipSuccess) return fail();      // (the scratch raster is the handle's: the next call may come on another stream)
@@ -203,6 +168,21 @@ size_t qb3api::windows_device(decsp p, const void *d_src, const void *d_index, c
     return done;
 }
 
+bool qb3api::window_dequantize(decsp p, const Geometry &g, void *dst, size_t w, size_t h, size_t stride, hipStream_t st) {
+    Geometry gw = g;
+    gw.w = (uint32_t)w; gw.h = (uint32_t)h; gw.stride = stride;
+    return p->quanta <= 1 || !launch_dequantize(dst, gw, (int)p->type, p->quanta, st);
+}
+bool qb3api::windows_out(decsp p, const qb3x_window *wins, size_t n, std::vector<void *> &dsts) {
+    const size_t pix = p->nbands * szof(p->type);
+    std::vector<size_t> at(n + 1, 0);
+    for (size_t i = 0; i < n; i++) at[i + 1] = at[i] + ((wins[i].h * wins[i].w * pix + 3) & ~(size_t)3);
+    if (!p->d_wout.ensure(at[n])) return false;
+    dsts = std::vector<void *>(n);
+    for (size_t i = 0; i < n; i++) dsts[i] = (uint8_t *)p->d_wout.p + at[i];
+    return true;
+}
+
 // The same for a container in host memory and host destinations (paths, single: as above): STORED containers are cropped on the
 // host; else the whole container goes up ONCE (the stream and its table), the windows are decoded back to back into one device
 // buffer (each starts on a dword) and come down one by one, each with its stride
@@ -223,14 +203,9 @@ size_t qb3api::windows_host(decsp p, const qb3x_window *wins, size_t n, uint8_t 
     if (!device_ok()) { p->error = QB3E_LIBERR; return 0; }
     hipStream_t st = nullptr;
     std::vector<qb3x_window> dw(wins, wins + n);
-    size_t wbytes = 0;
-    for (size_t i = 0; i < n; i++) wbytes += (wins[i].h * wins[i].w * pix + 3) & ~(size_t)3;
-    if (!p->d_wsrc.ensure(csize + 8) || !p->d_wout.ensure(wbytes)) { p->error = QB3E_LIBERR; return 0; }
-    wbytes = 0;
-    for (size_t i = 0; i < n; i++) {
-        dw[i].dst = (uint8_t *)p->d_wout.p + wbytes; dw[i].dst_stride = 0;
-        wbytes += (wins[i].h * wins[i].w * pix + 3) & ~(size_t)3;
-    }
+    std::vector<void *> dsts;
+    if (!p->d_wsrc.ensure(csize + 8) || !windows_out(p, wins, n, dsts)) { p->error = QB3E_LIBERR; return 0; }
+    for (size_t i = 0; i < n; i++) { dw[i].dst = dsts[i]; dw[i].dst_stride = 0; }
     if (!upload(p->stager, p->d_wsrc.p, p->s_start, csize, st)) { p->error = QB3E_LIBERR; return 0; }
     HIPOK(hipMemsetAsync((uint8_t *)p->d_wsrc.p + csize, 0, 8, st));      // (a stream that ends early reads as zeros behind its end)
     if (!windows_device(p, p->d_wsrc.p, nullptr, dw.data(), n, paths, single, st)) return 0;

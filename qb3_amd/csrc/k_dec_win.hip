@@ -31,32 +31,13 @@ namespace qb3dev {
 // ... for the strip of block rows of a window call (path 2), whose launch has checked the whole table: one lane
 __global__ void ix_tail_kernel(const DecArgs a) { if (threadIdx.x == 0) ix_tail_check(a); }
 
-template <int B, bool RGB, uint64_t ORDER, bool STEP>
-__global__ void __launch_bounds__(256) dec_win_kernel(const WinArgs wa) {
-    const DecArgs &a = wa.d;
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    if (blockIdx.x < wa.chk_n) {                        // the launch's first workgroups: a chunk of the container's table each
-        ix_check_chunk(a, wa.chk0 + blockIdx.x, (uint32_t *)smem);
-        return;
-    }
-    if (blockIdx.x == wa.chk_n) {                       // ... and one for the table's end
-        if (wa.tail_chunk) ix_check_chunk(a, (a.ix_K - 1) / a.ix_per_chunk, (uint32_t *)smem);
-        if (threadIdx.x == 0) ix_tail_check(a);
-        return;
-    }
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));    // (wave uniform: what follows from it stays in scalar registers)
-    win_decode_wave<B, RGB, ORDER, STEP>(a, wa.w, a.status, smem, wave, (blockIdx.x - wa.chk_n - 1) * 4 + wave);
-}
-
 uint64_t window_segments(const Geometry &g, const WinRect &r) {
     if (!g.seg_blocks || !r.w || !r.h || (uint64_t)r.x0 + r.w > g.w || (uint64_t)r.y0 + r.h > g.h) return 0;
-    WinDesc d;
-    window_desc(g, r, nullptr, &d);
-    const uint32_t bx0 = d.bx0, bx1 = d.bx1, by0 = d.by0, by1 = d.by1;
+    const WinBlocks b = window_blocks(g, r.x0, r.y0, r.w, r.h);
     // both ends of a row's range of segments grow with the row: what a row adds lies behind the last segment of the row above
     uint64_t n = 0, next = 0;
-    for (uint64_t by = by0; by <= by1; by++) {
-        const uint64_t s0 = (by * g.nbx + bx0) / g.seg_blocks, s1 = (by * g.nbx + bx1) / g.seg_blocks;
+    for (uint64_t by = b.by0; by <= b.by1; by++) {
+        const uint64_t s0 = (by * g.nbx + b.bx0) / g.seg_blocks, s1 = (by * g.nbx + b.bx1) / g.seg_blocks;
         const uint64_t lo = std::max(s0, next);
         if (s1 >= lo) { n += s1 - lo + 1; next = s1 + 1; }
     }
@@ -82,40 +63,17 @@ uint32_t window_launch_args(WinArgs &wa, const Geometry &g, const DecPlan &plan,
     DecArgs &a = wa.d;
     window_dec_args(a, g, plan, in32, in_bit0, in_bits, status, ix);
     window_desc(g, r, dst, &wa.w);
-    // table chunks an entry is read from: the first segment's to the one of the entry behind the last segment
-    const uint64_t first = ((uint64_t)wa.w.by0 * g.nbx + wa.w.bx0) / g.seg_blocks, last = std::min<uint64_t>(((uint64_t)wa.w.by1 * g.nbx + wa.w.bx1) / g.seg_blocks + 1, ix.K - 1);
-    wa.chk0 = (uint32_t)(first / ix.per_chunk);
+    uint32_t c0, c1;
+    window_chunk_range(g, WinBlocks{ wa.w.bx0, wa.w.bx1, wa.w.by0, wa.w.by1 }, ix.K, ix.per_chunk, &c0, &c1);
+    wa.chk0 = c0;
     const bool checked = a.ix_ver >= 3 || a.ix_check_heads;
-    wa.chk_n = checked ? (uint32_t)(last / ix.per_chunk) - wa.chk0 + 1 : 0;
-    wa.tail_chunk = checked && (ix.K - 1) / ix.per_chunk > last / ix.per_chunk;
+    wa.chk_n = checked ? c1 - c0 + 1 : 0;
+    wa.tail_chunk = checked && (ix.K - 1) / ix.per_chunk > c1;
     return wa.chk_n + 1 + (wa.w.nwaves + 3) / 4;
 }
 
-template <int B, bool RGB>
-static void launch_dec_win_b(const WinArgs &wa, dim3 grid, size_t lds, hipStream_t st) {
-    const bool step = wa.d.g.mode != CM_FTL, z = wa.d.g.order == ZCURVE;
-    const dim3 block(256);
-    if (!z && !step) hipLaunchKernelGGL((dec_win_kernel<B, RGB, HILBERT, false>), grid, block, lds, st, wa);
-    else if (!z && step) hipLaunchKernelGGL((dec_win_kernel<B, RGB, HILBERT, true>), grid, block, lds, st, wa);
-    else if (z && !step) hipLaunchKernelGGL((dec_win_kernel<B, RGB, ZCURVE, false>), grid, block, lds, st, wa);
-    else hipLaunchKernelGGL((dec_win_kernel<B, RGB, ZCURVE, true>), grid, block, lds, st, wa);
-}
-
-int launch_decode_window(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
-                         void *dst, const WinRect &r, uint32_t *status, void *stream, const IxTable &ix) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!decode_window_ok(g, plan, ix) || !window_segments(g, r) || r.stride < (uint64_t)r.w * g.bands) { set_error("window decode: not for this raster", 0); return -1; }
-    WinArgs wa = {};
-    const dim3 grid(window_launch_args(wa, g, plan, in32, in_bit0, in_bits, dst, r, status, ix));
-    HIPCHK(hipMemsetAsync(status, 0, 4, st));
-    {
-        ProfScope ps("dec_window", st);
-        if (g.bands == 1) launch_dec_win_b<1, false>(wa, grid, plan.lds_px, st);
-        else if (g.bands == 3) { if (plan.px_rgb) launch_dec_win_b<3, true>(wa, grid, plan.lds_px, st); else launch_dec_win_b<3, false>(wa, grid, plan.lds_px, st); }
-        else { if (plan.px_rgb) launch_dec_win_b<4, true>(wa, grid, plan.lds_px, st); else launch_dec_win_b<4, false>(wa, grid, plan.lds_px, st); }
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
+void win_u8_one(const Geometry &g, const DecPlan &plan, const WinArgs &wa, const WinLaunch &l) {
+    win_u8_pick(g, plan, [&](auto f) { win_launch(f, wa, l); });
 }
 
 int launch_window_tail_check(const Geometry &g, uint64_t in_bits, uint32_t *status, void *stream, const IxTable &ix) {

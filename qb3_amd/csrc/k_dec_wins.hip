@@ -1,63 +1,55 @@
-// qb3_amd/csrc/k_dec_wins.hip -- a batch of windows of one raster in ONE launch: dec_win_kernel's work (qb3_win.h, k_dec_win.hip) for
+// qb3_amd/csrc/k_dec_wins.hip -- a batch of windows of one raster in ONE launch: the single kernel's work (qb3_win.h, k_dec_win.hip) for
 // many rectangles at once.  A tile server asks for tens of small windows of a raster it keeps in device memory; each is a hundred
 // waves or so, far from filling the device, and each single call pays a launch, a status word and a wait.
 //   * DESCRIPTORS  What the single kernel takes as arguments about its window (WinDesc) sits in an array in device memory, one
 //     entry a window, with the exclusive prefix of the windows' wave counts.  Wave g of the launch finds its window by a binary
 //     search for the last entry whose prefix is not above g; g and the search are wave uniform, the entry is read with scalar
 //     loads, and from there on the wave is wave g - prefix of that window: mapping, de-duplication, clipping and stores are
-//     win_decode_wave's.
+//     the wave routine's.
 //   * TRUST  The host merges the ranges of table chunks the windows read entries from into a sorted list without duplicates (the
 //     table's last chunk is always in it); the launch's first workgroups check one chunk of the list each, one more compares the
 //     table's last entry with the stream's length.  Their failures go to a call-wide status word: the table is then not this
 //     stream's, for any window.
 //   * STATUS  A word per window: a wave raises bits in the word of its window only, so one bad segment costs the windows that hold
 //     it the shortcut and leaves the others alone.
+// Here too, because this file is the one every window call links: the 8-bit family's record, the choice of the family and the three
+// launchers every family goes through.
+#include <string>
 #include "qb3_win.h"
 
 namespace qb3dev {
 
-template <int B, bool RGB, uint64_t ORDER, bool STEP>
-__global__ void __launch_bounds__(256) dec_wins_kernel(const WinBatchArgs ba) {
-    const DecArgs &a = ba.d;
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    if (blockIdx.x < ba.chk_n) {                        // the launch's first workgroups: a chunk of the container's table each
-        ix_check_chunk(a, ba.chunks[blockIdx.x], (uint32_t *)smem);
-        return;
-    }
-    if (blockIdx.x < ba.chk_n + ba.tail) {              // ... and one for the table's end
-        if (threadIdx.x == 0) ix_tail_check(a);
-        return;
-    }
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t gw = (blockIdx.x - ba.chk_n - ba.tail) * 4 + wave;      // (wave uniform, as is all of the search)
-    // the last window whose first wave is not behind gw (wave0 grows strictly: every window has a wave; window 0 starts at 0).
-    // A wave behind the last window's waves lands in the last window and leaves there (wid >= nwaves).
-    uint32_t lo = 0, hi = ba.nwin;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (ba.wins[mid].wave0 <= gw) lo = mid; else hi = mid;
-    }
-    lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
-    const WinDesc w = ba.wins[lo];                      // sixteen dwords, read before anything is stored
-    win_decode_wave<B, RGB, ORDER, STEP>(a, w, ba.wstatus + lo, smem, wave, gw - w.wave0);
+void win_u8_batch(const Geometry &g, const DecPlan &plan, const WinBatchArgs &ba, const WinLaunch &l) {
+    win_u8_pick(g, plan, [&](auto f) { win_launch(f, ba, l); });
+}
+// 8-bit grey / RGB / RGBA rasters, FTL / BASE: dec_px_kernel's BL branch a segment, byte and dword stores to any address
+const WinKernels &win_u8() {      // (in a function: host data, not for the device side of this file)
+    static const WinKernels k = { decode_window_ok, 0, window_align_any, nullptr, window_lds_px, "", "dec_window", "dec_window_ranged", win_u8_one, win_u8_batch, win_u8_ranged };
+    return k;
 }
 
-template <int B, bool RGB>
-static void launch_dec_wins_b(const WinBatchArgs &ba, dim3 grid, size_t lds, hipStream_t st) {
-    const bool step = ba.d.g.mode != CM_FTL, z = ba.d.g.order == ZCURVE;
-    const dim3 block(256);
-    if (!z && !step) hipLaunchKernelGGL((dec_wins_kernel<B, RGB, HILBERT, false>), grid, block, lds, st, ba);
-    else if (!z && step) hipLaunchKernelGGL((dec_wins_kernel<B, RGB, HILBERT, true>), grid, block, lds, st, ba);
-    else if (z && !step) hipLaunchKernelGGL((dec_wins_kernel<B, RGB, ZCURVE, false>), grid, block, lds, st, ba);
-    else hipLaunchKernelGGL((dec_wins_kernel<B, RGB, ZCURVE, true>), grid, block, lds, st, ba);
+const WinKernels *window_family(const Geometry &g, const DecPlan &plan, const IxTable &ix, unsigned mask) {
+    for (const WinKernels *k : { &win_u8(), &win_u16(), &win_cf8(), &win_unit(), &win_cfu() })
+        if ((!k->bit || (mask & k->bit)) && k->ok(g, plan, ix)) return k;
+    return nullptr;
+}
+
+void window_chunk_list(const Geometry &g, uint32_t K, uint32_t per_chunk, const WinRect *rects, size_t n, std::vector<uint32_t> &chunks) {
+    chunks.clear();
+    for (size_t i = 0; i < n; i++) {
+        uint32_t c0, c1;
+        window_chunk_range(g, window_blocks(g, rects[i].x0, rects[i].y0, rects[i].w, rects[i].h), K, per_chunk, &c0, &c1);
+        for (uint32_t c = c0; c <= c1; c++) chunks.push_back(c);
+    }
+    chunks.push_back((K - 1) / per_chunk);              // the tail check reads the table's last entry
+    std::sort(chunks.begin(), chunks.end());
+    chunks.erase(std::unique(chunks.begin(), chunks.end()), chunks.end());
 }
 
 size_t window_batch_plan(const Geometry &g, const IxTable &ix, const WinRect *rects, void *const *dsts, size_t n, void *descs,
                          std::vector<uint32_t> &chunks, uint64_t *segments) {
     WinDesc *d = (WinDesc *)descs;
-    const bool checked = ix.version >= 3 || ix.check_heads;
     uint64_t waves = 0, segs = 0;
-    chunks.clear();
     for (size_t i = 0; i < n; i++) {
         window_desc(g, rects[i], dsts[i], &d[i]);
         // a launch ends in front of the window that would take it beyond WIN_LAUNCH_WAVES; the prefix starts again there
@@ -65,32 +57,69 @@ size_t window_batch_plan(const Geometry &g, const IxTable &ix, const WinRect *re
         d[i].wave0 = (uint32_t)waves;
         waves += d[i].nwaves;
         segs += window_segments(g, rects[i]);
-        if (checked) {      // table chunks an entry is read from: the first segment's to the one of the entry behind the last segment
-            const uint64_t first = ((uint64_t)d[i].by0 * g.nbx + d[i].bx0) / g.seg_blocks, last = std::min<uint64_t>(((uint64_t)d[i].by1 * g.nbx + d[i].bx1) / g.seg_blocks + 1, ix.K - 1);
-            for (uint64_t c = first / ix.per_chunk; c <= last / ix.per_chunk; c++) chunks.push_back((uint32_t)c);
-        }
     }
-    if (checked) {
-        chunks.push_back((ix.K - 1) / ix.per_chunk);    // the tail check reads the table's last entry
-        std::sort(chunks.begin(), chunks.end());
-        chunks.erase(std::unique(chunks.begin(), chunks.end()), chunks.end());
-    }
+    chunks.clear();
+    if (ix.version >= 3 || ix.check_heads) window_chunk_list(g, ix.K, ix.per_chunk, rects, n, chunks);
     if (segments) *segments = segs;
     return chunks.size();
 }
 
-int launch_decode_windows(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
+static int window_refused(const WinKernels &k, const char *form) {
+    set_error((std::string(k.noun) + form + ": not for this raster").c_str(), 0);
+    return -1;
+}
+
+int launch_decode_window(const WinKernels &k, const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
+                         void *dst, const WinRect &r, uint32_t *status, void *stream, const IxTable &ix) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!k.ok(g, plan, ix) || !window_segments(g, r) || r.stride < (uint64_t)r.w * g.bands || ((uintptr_t)dst & (k.align(g) - 1)))
+        return window_refused(k, "window decode");
+    WinArgs wa = {};
+    const uint32_t grid = window_launch_args(wa, g, plan, in32, in_bit0, in_bits, dst, r, status, ix);
+    if (k.more_args) k.more_args(wa.d, plan);
+    HIPCHK(hipMemsetAsync(status, 0, 4, st));
+    {
+        ProfScope ps(k.prof, st);
+        k.one(g, plan, wa, WinLaunch{ grid, k.lds(g, plan), stream });
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int launch_decode_windows(const WinKernels &k, const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
                           const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
                           uint32_t *d_status, void *stream, const IxTable &ix) {
     hipStream_t st = (hipStream_t)stream;
-    if (!decode_window_ok(g, plan, ix) || !n) { set_error("window batch: not for this raster", 0); return -1; }
+    if (!k.ok(g, plan, ix) || !n) return window_refused(k, "window batch");
     WinBatchArgs ba = {};
     window_dec_args(ba.d, g, plan, in32, in_bit0, in_bits, d_status, ix);
-    window_batch_launches(ba, h_descs, d_descs, n, d_chunks, nchunks, d_status, [&](const WinBatchArgs &ba, dim3 grid) {
-        ProfScope ps("dec_window", st);
-        if (g.bands == 1) launch_dec_wins_b<1, false>(ba, grid, plan.lds_px, st);
-        else if (g.bands == 3) { if (plan.px_rgb) launch_dec_wins_b<3, true>(ba, grid, plan.lds_px, st); else launch_dec_wins_b<3, false>(ba, grid, plan.lds_px, st); }
-        else { if (plan.px_rgb) launch_dec_wins_b<4, true>(ba, grid, plan.lds_px, st); else launch_dec_wins_b<4, false>(ba, grid, plan.lds_px, st); }
+    if (k.more_args) k.more_args(ba.d, plan);
+    ba.chunks = d_chunks;
+    // in front of the first launch's waves: a workgroup for every chunk of the list and one for the tail check
+    window_launches(ba, h_descs, d_descs, n, d_status, (uint32_t)nchunks + 1, [&](uint32_t grid, bool head) {
+        ba.chk_n = head ? (uint32_t)nchunks : 0; ba.tail = head ? 1 : 0;
+        ProfScope ps(k.prof, st);
+        k.batch(g, plan, ba, WinLaunch{ grid, k.lds(g, plan), stream });
+    });
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int launch_decode_windows_ranged(const WinKernels &k, const Geometry &g, const DecPlan &plan, uint32_t in_bit0, uint64_t in_bits, const void *h_descs,
+                                 const void *d_descs, size_t n, const void *d_pieces, size_t npieces, const void *d_entries, const uint32_t *d_words,
+                                 uint32_t *d_status, void *stream, const IxTable &ix) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!k.ranged || !k.ok(g, plan, ix) || !n || !npieces || npieces > 0xffffffffull) return window_refused(k, "ranged window batch");
+    WinRangedArgs ra = {};
+    IxTable none = ix;
+    none.base = nullptr;            // (the table is not in device memory)
+    window_dec_args(ra.d, g, plan, nullptr, in_bit0, in_bits, d_status, none);
+    if (k.more_args) k.more_args(ra.d, plan);
+    ra.src.pieces = (const WinPiece *)d_pieces; ra.src.npieces = (uint32_t)npieces;
+    ra.src.ents = (const uint8_t *)d_entries; ra.src.words = d_words;
+    window_launches(ra, h_descs, d_descs, n, d_status, 0, [&](uint32_t grid, bool) {
+        ProfScope ps(k.prof_ranged, st);
+        k.ranged(g, plan, ra, WinLaunch{ grid, k.lds(g, plan), stream });
     });
     HIPCHK(hipGetLastError());
     return 0;

@@ -13,39 +13,8 @@
 
 namespace qb3dev {
 
-template <int BG, bool RGB, uint64_t ORDER, bool STEP>
-__global__ void __launch_bounds__(256, 4) dec_wins16_ranged_kernel(const WinRangedArgs ra) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t gw = blockIdx.x * 4 + wave;          // (wave uniform, as are both searches)
-    uint32_t lo = 0, hi = ra.nwin;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (ra.wins[mid].wave0 <= gw) lo = mid; else hi = mid;
-    }
-    lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
-    const WinDesc w = ra.wins[lo];
-    win16_decode_wave<BG, RGB, ORDER, STEP, WinSrcPieces>(ra.d, w, ra.wstatus + lo, smem, wave, gw - w.wave0, ra.src);
-}
-
-int launch_decode_windows16_ranged(const Geometry &g, const DecPlan &plan, uint32_t in_bit0, uint64_t in_bits, const void *h_descs, const void *d_descs,
-                                   size_t n, const void *d_pieces, size_t npieces, const void *d_entries, const uint32_t *d_words,
-                                   uint32_t *d_status, void *stream, const IxTable &ix) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!decode_window16_ok(g, plan, ix) || !n || !npieces || npieces > 0xffffffffull) { set_error("16-bit ranged window batch: not for this raster", 0); return -1; }
-    WinRangedArgs ra = {};
-    IxTable none = ix;
-    none.base = nullptr;            // (the table is not in device memory)
-    window_dec_args(ra.d, g, plan, nullptr, in_bit0, in_bits, d_status, none);
-    window16_dec_args(ra.d, plan);
-    ra.src.pieces = (const WinPiece *)d_pieces; ra.src.npieces = (uint32_t)npieces;
-    ra.src.ents = (const uint8_t *)d_entries; ra.src.words = d_words;
-    window_ranged_launches(ra, h_descs, d_descs, n, d_status, [&](const WinRangedArgs &args, dim3 grid) {
-        ProfScope ps("dec_window16_ranged", st);
-        QB3_WIN16_DISPATCH(dec_wins16_ranged_kernel, args);
-    });
-    HIPCHK(hipGetLastError());
-    return 0;
+void win16_ranged(const Geometry &g, const DecPlan &plan, const WinRangedArgs &ra, const WinLaunch &l) {
+    win16_pick(g, plan, [&](auto f) { win_launch(f, ra, l); });
 }
 
 }  // namespace qb3dev

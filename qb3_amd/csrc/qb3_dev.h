@@ -3,6 +3,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <algorithm>
 #include <vector>
 
 namespace qb3dev {
@@ -262,97 +263,94 @@ int launch_decode(const Geometry &g, const DecPlan &plan, const uint32_t *in32, 
 // lane-per-block decoder per range of segments, nothing else
 bool decode_strips_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix);
 
-// Window decode (k_dec_win.hip): a rectangle of the raster from the container's level-2 table, only the index segments that hold one
-// of its blocks.  x0, y0, w, h in raster pixels; stride: values between the rows of the destination, which receives the window alone.
+// Window decode: a rectangle of the raster from the container's restart table, only the index segments that hold one of its blocks
+// (mapping, clipping and trust: the head of k_dec_win.hip).  x0, y0, w, h in raster pixels; stride: values between the rows of the
+// destination, which receives the window alone.
 struct WinRect { uint32_t x0, y0, w, h; uint64_t stride; };
+// the window's blocks, both ends included, by the geometry rule: pixel x is held by block min(x / 4, nbx - 1) -- the last block column /
+// row is shifted, not padded.  The caller has checked that the window is not empty and lies inside the raster.
+struct WinBlocks { uint32_t bx0, bx1, by0, by1; };
+inline WinBlocks window_blocks(const Geometry &g, uint64_t x0, uint64_t y0, uint64_t w, uint64_t h) {
+    return WinBlocks{ (uint32_t)std::min<uint64_t>(x0 / 4, g.nbx - 1), (uint32_t)std::min<uint64_t>((x0 + w - 1) / 4, g.nbx - 1),
+                      (uint32_t)std::min<uint64_t>(y0 / 4, g.nby - 1), (uint32_t)std::min<uint64_t>((y0 + h - 1) / 4, g.nby - 1) };
+}
+// table chunks an entry of the window is read from: the chunk of its first segment's entry to the chunk of the entry behind its last
+// segment, whose position ends it (K entries, per_chunk a chunk)
+inline void window_chunk_range(const Geometry &g, const WinBlocks &b, uint32_t K, uint32_t per_chunk, uint32_t *c0, uint32_t *c1) {
+    const uint64_t first = ((uint64_t)b.by0 * g.nbx + b.bx0) / g.seg_blocks, last = std::min<uint64_t>(((uint64_t)b.by1 * g.nbx + b.bx1) / g.seg_blocks + 1, K - 1);
+    *c0 = (uint32_t)(first / per_chunk); *c1 = (uint32_t)(last / per_chunk);
+}
 // index segments of the raster that hold a block of the window (pure geometry: needs w, h, nbx, nby, seg_blocks; 0: the window is
-// empty or not inside the raster).  Pixel x is held by block min(x / 4, nbx - 1): the last block column / row is shifted, not padded.
+// empty or not inside the raster)
 uint64_t window_segments(const Geometry &g, const WinRect &r);
-// does the window kernel take this raster and table: what dec_px_kernel decodes from the entries alone (8-bit, 1/3/4 bands, FTL / BASE)
-bool decode_window_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix);
-// One launch (its first workgroups check the table chunks the window's entries are read from); status: a device word of the caller's,
-// zeroed here -- nonzero afterwards means "do not trust the window's bytes".  Does not synchronise.  Returns hipError_t as int.
-int launch_decode_window(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
-                         void *dst, const WinRect &r, uint32_t *status, void *stream, const IxTable &ix);
 // behind a strip of launch_decode (which has checked the table): status bit 2 when the table's last entry lies beyond the stream's end
 // -- a stream cut short, which only the whole decode may judge
 int launch_window_tail_check(const Geometry &g, uint64_t in_bits, uint32_t *status, void *stream, const IxTable &ix);
 
-// A batch of windows of one raster (k_dec_wins.hip): one launch decodes all of them, a status word per window.
-// window_batch_plan fills n descriptors of WIN_DESC_BYTES each at `descs` (host memory the caller then copies to the device as it
-// is), the sorted list of table chunks the launch has to check, and the sum of the windows' segment counts; it returns the list's
-// length.  launch_decode_windows takes the descriptors' host and device copies, the chunk list on the device and n + 1 zeroed status
-// words (word 0: the table's checks, call wide; word 1 + i: window i).  Does not synchronise.  Returns hipError_t as int.
+// The window kernels come in FAMILIES, one per wave routine, each with a record (WinKernels) in the file that holds its kernels.  A
+// family's predicate asks decode_strips_ok, a table with the fields its whole-raster decoder takes a segment from alone, and ONE answer
+// of aligned_dec_kernel -- so at most one family takes a raster:
+//   family   record in                 rasters (aligned_dec_kernel)                         table                 switch            dst     ranged
+//   win_u8   k_dec_wins.hip            8-bit, 1/3/4 bands, FTL / BASE (px)                  level 2               always on         any     yes
+//   win_u16  k_dec_win16.hip           16-bit, 1/2/3/4/6/8 bands, FTL / BASE (px16)         level 2, version 3    U16               2       yes
+//   win_cf8  k_dec_win_best.hip        8-bit, 1/3/4 bands, common factor (px_best)          level 1 or 2          CF8               any     yes
+//   win_unit k_dec_win_unit.hip        lane-per-unit and one-band 32/64-bit rasters,        level 2, version 3    UNIT              value   no
+//                                      FTL / BASE (pxu, pxw), window_unit_geometry_ok
+//   win_cfu  k_dec_win_best_unit.hip   the common-factor streams of such shapes and of      level 1 or 2, v. 3    CFU               value   no
+//                                      one-band 16-bit rasters (pxu_best, pxw_best), window_unit_geometry_ok
+// (switch: the bit of qb3x_set_decoder_window_kernels (include/qb3x.h) the handle must have set; dst: bytes every destination must be a multiple of.)
+// Each family has up to three FORMS, one kernel shell each (qb3_win.h): a single window as kernel arguments, a batch of windows from a
+// descriptor array, a batch decoded from fetched pieces of the container (ranged).  A dispatcher launches the shell's instantiation
+// that the geometry and the plan select.
+struct DecArgs; struct WinArgs; struct WinBatchArgs; struct WinRangedArgs;      // (qb3_kernels.h, qb3_win.h)
+struct WinLaunch { uint32_t grid; size_t lds; void *stream; };
+struct WinKernels {
+    bool (*ok)(const Geometry &, const DecPlan &, const IxTable &);     // does the raster and its table qualify
+    unsigned bit;                                                       // the switch that enables the family (0: always on)
+    uint32_t (*align)(const Geometry &);                                // bytes every destination must be a multiple of (a power of two)
+    void (*more_args)(DecArgs &, const DecPlan &);                      // what its wave routine takes besides window_dec_args (null: nothing)
+    size_t (*lds)(const Geometry &, const DecPlan &);                   // dynamic LDS of a launch
+    const char *noun, *prof, *prof_ranged;                              // in front of "window ..." in error texts; profile names
+    void (*one)(const Geometry &, const DecPlan &, const WinArgs &, const WinLaunch &);
+    void (*batch)(const Geometry &, const DecPlan &, const WinBatchArgs &, const WinLaunch &);
+    void (*ranged)(const Geometry &, const DecPlan &, const WinRangedArgs &, const WinLaunch &);    // null: the family has no ranged form
+};
+const WinKernels &win_u8(), &win_u16(), &win_cf8(), &win_unit(), &win_cfu();
+bool decode_window_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix);        // win_u8's predicate (k_dec_win.hip)
+// The family that takes a raster and its table on a handle with these switches (mask), or null.  The order of the questions
+// carries no meaning: every predicate requires another answer of aligned_dec_kernel (pick_dec_kernel, k_dec_launch.hip, returns one
+// DecKernel for a geometry and plan: px; px16; px_best; pxu or pxw; pxu_best or pxw_best), so no two families qualify.  The caller
+// applies the family's alignment to its destinations; one that misses it leaves no family at all, since no other can qualify.
+const WinKernels *window_family(const Geometry &g, const DecPlan &plan, const IxTable &ix, unsigned mask);
+
+// One window, one launch (its first workgroups check the table chunks the window's entries are read from); status: a device word of the
+// caller's, zeroed here -- nonzero afterwards means "do not trust the window's bytes".  Does not synchronise.  Returns hipError_t as int.
+int launch_decode_window(const WinKernels &k, const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
+                         void *dst, const WinRect &r, uint32_t *status, void *stream, const IxTable &ix);
+// A batch of windows of one raster: one launch decodes all of them, a status word per window.  window_batch_plan fills n descriptors of
+// WIN_DESC_BYTES each at `descs` (host memory the caller then copies to the device as it is), the sorted list of table chunks the
+// launch has to check (window_chunk_list), and the sum of the windows' segment counts; it returns the list's length.
+// launch_decode_windows takes the descriptors' host and device copies, the chunk list on the device and n + 1 zeroed status words
+// (word 0: the table's checks, call wide; word 1 + i: window i).  Does not synchronise.  Returns hipError_t as int.
 constexpr size_t WIN_DESC_BYTES = 64;
 // (WIN_LAUNCH_WAVES, the waves of one launch: above, at window_unit_geometry_ok)
+void window_chunk_list(const Geometry &g, uint32_t K, uint32_t per_chunk, const WinRect *rects, size_t n, std::vector<uint32_t> &chunks);     // ... and the table's last chunk: the tail check reads the last entry
 size_t window_batch_plan(const Geometry &g, const IxTable &ix, const WinRect *rects, void *const *dsts, size_t n, void *descs,
                          std::vector<uint32_t> &chunks, uint64_t *segments);
-int launch_decode_windows(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
+int launch_decode_windows(const WinKernels &k, const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
                           const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
                           uint32_t *d_status, void *stream, const IxTable &ix);
-// The 16-bit window kernels (k_dec_win16.hip): rasters of 1, 2, 3, 4, 6 or 8 bands, FTL / BASE, whose level-2 table (version 3) carries
-// the lane fields dec_px16_kernel decodes a segment from alone.  decode_window16_ok: does the raster and its table qualify (the host
-// also asks the handle's switch, qb3x_set_decoder_window_kernels, before it takes them).  The launchers are their 8-bit counterparts'
-// in everything but the kernels: arguments, descriptors (window_batch_plan), status words; dst must be halfword aligned.
-bool decode_window16_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix);
-int launch_decode_window16(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
-                           void *dst, const WinRect &r, uint32_t *status, void *stream, const IxTable &ix);
-int launch_decode_windows16(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
-                            const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
-                            uint32_t *d_status, void *stream, const IxTable &ix);
-// The window kernels of the 8-bit common-factor modes (k_dec_win_best.hip): rasters of 1, 3 or 4 bands in CM_BEST whose table (level 1
-// or 2) carries the block fields dec_px_best_kernel decodes a segment from alone.  decode_window_best_ok: does the raster and its table
-// qualify (the host also asks the handle's switch, QB3X_WINK_CF8, before it takes them).  The launchers are launch_decode_window's and
-// launch_decode_windows' in everything but the kernels; dst needs no alignment.
-bool decode_window_best_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix);
-int launch_decode_window_best(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
-                              void *dst, const WinRect &r, uint32_t *status, void *stream, const IxTable &ix);
-int launch_decode_windows_best(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
-                               const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
-                               uint32_t *d_status, void *stream, const IxTable &ix);
-// The window kernels of the lane-per-unit rasters and of one-band 32/64-bit rasters (k_dec_win_unit.hip): FTL / BASE rasters whose aligned
-// decode kernel is DecKernel::pxu or DecKernel::pxw and whose level-2 table (version 3) carries the twelve-bit unit lengths those kernels
-// decode a segment from alone, on a geometry one launch holds (window_unit_geometry_ok).  decode_window_unit_ok: does the raster and its
-// table qualify (the host also asks the handle's switch, QB3X_WINK_UNIT, before it takes them).  The launchers are their 16-bit
-// counterparts' in everything but the kernels; dst must be value aligned.
-bool decode_window_unit_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix);
-int launch_decode_window_unit(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
-                              void *dst, const WinRect &r, uint32_t *status, void *stream, const IxTable &ix);
-int launch_decode_windows_unit(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
-                               const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
-                               uint32_t *d_status, void *stream, const IxTable &ix);
-// The window kernels of the common-factor streams of such shapes (k_dec_win_best_unit.hip): rasters in CM_BEST whose aligned decode kernel
-// is DecKernel::pxu_best or DecKernel::pxw_best and whose table (level 1 or 2, version 3) carries the three-byte field per unit those
-// kernels decode a segment from alone, on a geometry one launch holds.  decode_window_best_unit_ok: does the raster and its table qualify
-// (the host also asks the handle's switch, QB3X_WINK_CFU, before it takes them).  The launchers are launch_decode_window_unit's and
-// launch_decode_windows_unit's in everything but the kernels; dst must be value aligned.
-bool decode_window_best_unit_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix);
-int launch_decode_window_best_unit(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
-                                   void *dst, const WinRect &r, uint32_t *status, void *stream, const IxTable &ix);
-int launch_decode_windows_best_unit(const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
-                                    const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
-                                    uint32_t *d_status, void *stream, const IxTable &ix);
-// The same from PIECES of the container (k_dec_wins_ranged.hip; api_ranged.cpp fetches them): d_pieces: npieces >= 1 pieces sorted by
-// first segment, each a run of consecutive segments { seg0, nseg, ent0, word0, stream word of its first packed word (low, high),
-// nwords, 0 }; d_entries: the compact array of table entries (ix.entry_bytes each), nseg + 1 per piece from index ent0; d_words: the
-// pieces' stream words from index word0, counted as launch_decode's in32 counts them (word 0 holds the bit in_bit0 names).  The caller
-// vouches that ent0 + nseg + 1 and word0 + nwords stay inside the two arrays: the kernel reads nothing outside them.  The descriptors
-// are window_batch_plan's; status words as above, word 0 is not written (the table was checked on the host).  ix: the table's shape
-// (its base only has to be non-null).
+// The same from PIECES of the container (api_ranged.cpp fetches them), for a family that has the form: d_pieces: npieces >= 1 pieces
+// sorted by first segment, each a run of consecutive segments { seg0, nseg, ent0, word0, stream word of its first packed word (low,
+// high), nwords, 0 }; d_entries: the compact array of table entries (ix.entry_bytes each), nseg + 1 per piece from index ent0; d_words:
+// the pieces' stream words from index word0, counted as launch_decode's in32 counts them (word 0 holds the bit in_bit0 names).  The
+// caller vouches that ent0 + nseg + 1 and word0 + nwords stay inside the two arrays: the kernel reads nothing outside them.  The
+// descriptors are window_batch_plan's; status words as above, word 0 is not written (the table was checked on the host).  ix: the
+// table's shape (its base only has to be non-null).  Destinations aligned as the family asks.
 constexpr size_t WIN_PIECE_BYTES = 32;
-int launch_decode_windows_ranged(const Geometry &g, const DecPlan &plan, uint32_t in_bit0, uint64_t in_bits, const void *h_descs, const void *d_descs,
-                                 size_t n, const void *d_pieces, size_t npieces, const void *d_entries, const uint32_t *d_words,
+int launch_decode_windows_ranged(const WinKernels &k, const Geometry &g, const DecPlan &plan, uint32_t in_bit0, uint64_t in_bits, const void *h_descs,
+                                 const void *d_descs, size_t n, const void *d_pieces, size_t npieces, const void *d_entries, const uint32_t *d_words,
                                  uint32_t *d_status, void *stream, const IxTable &ix);
-// ... and of a 16-bit raster the 16-bit window kernels take (k_dec_wins16_ranged.hip; decode_window16_ok): the same arguments, the
-// raster's own blocks per segment, every destination halfword aligned
-int launch_decode_windows16_ranged(const Geometry &g, const DecPlan &plan, uint32_t in_bit0, uint64_t in_bits, const void *h_descs, const void *d_descs,
-                                   size_t n, const void *d_pieces, size_t npieces, const void *d_entries, const uint32_t *d_words,
-                                   uint32_t *d_status, void *stream, const IxTable &ix);
-// ... and of an 8-bit common-factor raster the window kernels of k_dec_win_best.hip take (k_dec_wins_best_ranged.hip;
-// decode_window_best_ok): the same arguments, entries with block fields, destinations on any address
-int launch_decode_windows_best_ranged(const Geometry &g, const DecPlan &plan, uint32_t in_bit0, uint64_t in_bits, const void *h_descs, const void *d_descs,
-                                      size_t n, const void *d_pieces, size_t npieces, const void *d_entries, const uint32_t *d_words,
-                                      uint32_t *d_status, void *stream, const IxTable &ix);
 
 // Reindex (k_reindex.hip): the table chunks this library's encoder writes for a raster, made from the index a plain walk of its stream
 // has rebuilt (launch_decode with index == nullptr leaves it in ws behind the status words), and the new container around them.

@@ -119,7 +119,7 @@ struct decs {
     DevBuf d_win, d_wst, d_wout, d_wsrc;               // window calls: the raster a strip or a whole decode goes to before the crop; the window kernel's status word; a host call's window and container
     int win_path = 0;                                  // ... which way the last one went (qb3x_last_window_path) and how many segments it decoded
     size_t win_segs = 0;
-    unsigned win_kernels = 0;                          // qb3x_set_decoder_window_kernels: rasters beyond path 1's own that take a window kernel (QB3X_WINK_*)
+    unsigned win_kernels = 0;                          // qb3x_set_decoder_window_kernels: rasters beyond path 1's own that take a window kernel (the families' switches)
     DevBuf d_wdesc;                                    // a batch of windows: descriptors and the list of table chunks to check, as uploaded
     PinBuf h_wdesc, h_wst;                             // ... their pinned host copy (one copy up), and the status words (one copy back)
     std::vector<uint8_t> wins_path;                    // ... per window outcome of the last batch call (0: not written, else its path)
@@ -166,9 +166,34 @@ decsp read_start_impl(void *source, size_t hdr_avail, size_t source_size, size_t
 qb3dev::IxTable handle_table(const decs *p, const uint8_t *base);
 qb3dev::Geometry decoder_geometry(const decs *p, size_t w, size_t h, size_t stride);
 
+// what the window calls say once (api_window.cpp, api_ranged.cpp): values between the destination's rows; is the rectangle inside the raster
+inline size_t win_stride(const decs *p, const qb3x_window &w) { return w.dst_stride ? w.dst_stride : w.w * p->nbands; }
+inline bool window_inside(const decs *p, size_t x0, size_t y0, size_t w, size_t h) {
+    return w && h && x0 < p->xsize && w <= p->xsize - x0 && y0 < p->ysize && h <= p->ysize - y0;
+}
+// sorts ranges [first, second) and merges those that overlap, touch or lie within `gap` of each other
+template <class T> inline void merge_ranges(std::vector<std::pair<T, T>> &r, T gap = 0) {
+    std::sort(r.begin(), r.end());
+    size_t m = 0;
+    for (size_t i = 1; i < r.size(); i++) {
+        if (r[i].first - std::min(r[i].first, r[m].second) <= gap) r[m].second = std::max(r[m].second, r[i].second);
+        else r[++m] = r[i];
+    }
+    if (!r.empty()) r.resize(m + 1);
+}
+// the family of window kernels that takes a raster (qb3_dev.h: window_family), if every one of these device destinations meets its
+// alignment; else none, and the call goes the way of a raster no family takes
+inline const qb3dev::WinKernels *family_if_aligned(const qb3dev::WinKernels *fam, const qb3dev::Geometry &g, const qb3x_window *wins, size_t n) {
+    for (size_t i = 0; fam && i < n; i++) if ((uintptr_t)wins[i].dst & (fam->align(g) - 1)) fam = nullptr;
+    return fam;
+}
+
 // api_window.cpp: handle and rectangles of a window call (false: p->error is set); the windows of a container in device / host memory
-// (paths: a zeroed byte per window, which receives the path its pixels came by)
+// (paths: a zeroed byte per window, which receives the path its pixels came by); host destinations' stand-ins in the handle's d_wout,
+// back to back with tight rows, each on a dword (false: no memory); the window as a raster of its own, dequantised (false: a HIP failure)
 bool windows_check(decsp p, const qb3x_window *wins, size_t n, bool host);
+bool windows_out(decsp p, const qb3x_window *wins, size_t n, std::vector<void *> &dsts);
+bool window_dequantize(decsp p, const qb3dev::Geometry &g, void *dst, size_t w, size_t h, size_t stride, hipStream_t st);
 size_t windows_device(decsp p, const void *d_src, const void *d_index, const qb3x_window *wins, size_t n, uint8_t *paths, bool single, hipStream_t st);
 size_t windows_host(decsp p, const qb3x_window *wins, size_t n, uint8_t *paths, bool single);
 

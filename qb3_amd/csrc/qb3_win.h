@@ -1,7 +1,11 @@
-// qb3_amd/csrc/qb3_win.h -- what the window kernels share (k_dec_win.hip: one window a launch; k_dec_wins.hip: a batch of windows a
-// launch): the per-window numbers, the check of the table's end, and the wave's work -- a segment decoded from its table entry, its
-// blocks clipped to the window and stored.  The comment at the head of k_dec_win.hip describes mapping, clipping and trust.
+// qb3_amd/csrc/qb3_win.h -- what the window kernels of every family share (qb3_dev.h lists the families): the per-window numbers, the
+// arguments and the split of a batch into launches, the two sources a wave reads from, the check of the table's end, and -- at the
+// end -- the three kernel SHELLS, one per form, that every family instantiates over its wave routine.  Then the 8-bit family's own:
+// the wave's work (a segment decoded from its table entry, its blocks clipped to the window and stored) and its instantiations.
+// The comment at the head of k_dec_win.hip describes mapping, clipping and trust.
 #pragma once
+#include <type_traits>
+#include "../../include/qb3x.h"
 #include "qb3_px.h"
 
 namespace qb3dev {
@@ -23,10 +27,10 @@ static_assert(sizeof(WinDesc) == 64, "WinDesc is read with scalar loads of sixte
 inline void window_desc(const Geometry &g, const WinRect &r, void *dst, WinDesc *w) {
     w->dst = (uint8_t *)dst; w->dstride = r.stride * g.tsz;
     w->wx0 = r.x0; w->wy0 = r.y0; w->wx1 = r.x0 + r.w; w->wy1 = r.y0 + r.h;
-    w->bx0 = std::min(r.x0 / 4, g.nbx - 1); w->bx1 = std::min((r.x0 + r.w - 1) / 4, g.nbx - 1);
-    w->by0 = std::min(r.y0 / 4, g.nby - 1); w->by1 = std::min((r.y0 + r.h - 1) / 4, g.nby - 1);
+    const WinBlocks b = window_blocks(g, r.x0, r.y0, r.w, r.h);
+    w->bx0 = b.bx0; w->bx1 = b.bx1; w->by0 = b.by0; w->by1 = b.by1;
     // the most segments the run of bx1 - bx0 + 1 blocks of a row touches: it starts anywhere in a segment, unless rows start where segments do
-    // (NB blocks a segment: 64 for the 8-bit kernels, 64 / band groups for the 16-bit ones)
+    // (NB blocks a segment: 64 for the two 8-bit families, 64 / band groups for the 16-bit one, 64 / bands for the lane-per-unit ones)
     const uint32_t n = w->bx1 - w->bx0 + 1, NB = g.seg_blocks;
     w->per_row = (g.nbx % NB == 0) ? (w->bx0 % NB + n - 1) / NB + 1 : (n + NB - 2) / NB + 1;
     w->nwaves = (w->by1 - w->by0 + 1) * w->per_row;
@@ -36,14 +40,14 @@ inline void window_desc(const Geometry &g, const WinRect &r, void *dst, WinDesc 
 void window_dec_args(DecArgs &a, const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
                      uint32_t *status, const IxTable &ix);
 
-// what the single kernels take (dec_win_kernel, dec_win16_kernel) ...
+// what the single shell takes (win_one_kernel) ...
 struct WinArgs {
     DecArgs d;                      // stream, table, status word, staging capacity: as dec_px_kernel takes them
     WinDesc w;                      // the window: destination, rectangle in pixels and blocks, waves (qb3_win.h)
     uint32_t chk0, chk_n;           // table chunks the launch's first chk_n workgroups check, from chunk chk0
     uint32_t tail_chunk;            // the workgroup behind them checks the table's last chunk too (it is not one of those)
 };
-// ... and the batch kernels (dec_wins_kernel, dec_wins16_kernel)
+// ... and the batch shell (win_batch_kernel)
 struct WinBatchArgs {
     DecArgs d;                      // stream, table, staging capacity; d.status: the call-wide word
     const WinDesc *wins;            // the launch's windows, wave0 counted from the launch's first window
@@ -54,19 +58,18 @@ struct WinBatchArgs {
 // fills wa for one window (status: zeroed by the caller's launch) and returns the launch's workgroups: the chunk checks, the table's end, the waves
 uint32_t window_launch_args(WinArgs &wa, const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
                             void *dst, const WinRect &r, uint32_t *status, const IxTable &ix);
-// the launches of a batch (one, unless the waves exceed WIN_LAUNCH_WAVES: window_batch_plan's prefixes start again there); ba.d is filled,
-// launch(ba, grid) makes one
-template <class Launch>
-inline void window_batch_launches(WinBatchArgs &ba, const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
-                                  uint32_t *d_status, Launch launch) {
+// the launches of a batch, ranged or not (one, unless the waves exceed WIN_LAUNCH_WAVES: window_batch_plan's prefixes start again there):
+// the windows of each are put into args, then launch(grid, head) makes it -- `front` workgroups in the first launch of the call (head:
+// the table's checks), none in the later ones, then a workgroup for every four waves
+template <class Args, class Launch>
+inline void window_launches(Args &args, const void *h_descs, const void *d_descs, size_t n, uint32_t *d_status, uint32_t front, Launch launch) {
     const WinDesc *h = (const WinDesc *)h_descs;
     for (size_t first = 0; first < n;) {
         size_t end = first + 1;
         while (end < n && h[end].wave0 != 0) end++;
         const uint64_t waves = (uint64_t)h[end - 1].wave0 + h[end - 1].nwaves;
-        ba.wins = (const WinDesc *)d_descs + first; ba.wstatus = d_status + 1 + first; ba.nwin = (uint32_t)(end - first);
-        ba.chunks = d_chunks; ba.chk_n = first ? 0 : (uint32_t)nchunks; ba.tail = first ? 0 : 1;
-        launch(ba, dim3((uint32_t)(ba.chk_n + ba.tail + (waves + 3) / 4)));
+        args.wins = (const WinDesc *)d_descs + first; args.wstatus = d_status + 1 + first; args.nwin = (uint32_t)(end - first);
+        launch((uint32_t)((first ? 0 : front) + (waves + 3) / 4), first == 0);
         first = end;
     }
 }
@@ -131,7 +134,7 @@ struct WinSrcPieces {
         return words[pc.word0 + (uint32_t)(w - ((uint64_t)pc.sw0_hi << 32 | pc.sw0_lo))];      // (behind the container's end a piece has no words: holds() said no)
     }
 };
-// what the ranged kernels take (dec_wins_ranged_kernel, dec_wins16_ranged_kernel)
+// what the ranged shell takes (win_ranged_kernel)
 struct WinRangedArgs {
     DecArgs d;                      // geometry, stream length, staging capacity, entry size; d.in32 and d.ix are not used
     const WinDesc *wins;            // the launch's windows, wave0 counted from the launch's first window
@@ -139,20 +142,87 @@ struct WinRangedArgs {
     WinSrcPieces src;               // pieces, entries, packed words
     uint32_t nwin;
 };
-// the launches of a ranged batch, split as window_batch_launches splits; no check workgroups (the host verified the chunks); ra.d and
-// ra.src are filled, launch(ra, grid) makes one
-template <class Launch>
-inline void window_ranged_launches(WinRangedArgs &ra, const void *h_descs, const void *d_descs, size_t n, uint32_t *d_status, Launch launch) {
-    const WinDesc *h = (const WinDesc *)h_descs;
-    for (size_t first = 0; first < n;) {
-        size_t end = first + 1;
-        while (end < n && h[end].wave0 != 0) end++;
-        const uint64_t waves = (uint64_t)h[end - 1].wave0 + h[end - 1].nwaves;
-        ra.wins = (const WinDesc *)d_descs + first; ra.wstatus = d_status + 1 + first; ra.nwin = (uint32_t)(end - first);
-        launch(ra, dim3((uint32_t)((waves + 3) / 4)));
-        first = end;
+
+// The three SHELLS: what surrounds a family's wave routine in each form.  F names one instantiation of a family (WinU8 below, Win16,
+// WinCf8, WinUnit, WinCfu next to their wave routines): F::contig and F::pieces are the routine with the instantiation's template
+// arguments over the two sources, F::waves is the second number of the launch bounds (0: none given, the attributes are those of
+// __launch_bounds__(256)).  The two are constants of function type, so a shell calls the routine itself: with a forwarding function
+// in between, the four-band kernels of the 8-bit common-factor family took 96 registers and 8 bytes of scratch where they have 90
+// and none.
+// A family's pick(g, plan, visit) calls visit(F()) for the instantiation the geometry and the plan select; win_launch(f, args, l)
+// launches the shell over it that takes args.
+
+// the last window whose first wave is not behind gw (wave0 grows strictly: every window has a wave; window 0 starts at 0); gw and all
+// of the search are wave uniform.  A wave behind the last window's waves lands in the last window and leaves there (wid >= nwaves).
+__device__ __forceinline__ uint32_t win_search(const WinDesc *wins, uint32_t nwin, uint32_t gw) {
+    uint32_t lo = 0, hi = nwin;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (wins[mid].wave0 <= gw) lo = mid; else hi = mid;
     }
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
 }
+// one window, as kernel arguments (no descriptor goes up for a single call)
+template <class F>
+__global__ void __launch_bounds__(256, F::waves) win_one_kernel(const WinArgs wa) {
+    const DecArgs &a = wa.d;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    if (blockIdx.x < wa.chk_n) {                        // the launch's first workgroups: a chunk of the container's table each
+        ix_check_chunk(a, wa.chk0 + blockIdx.x, (uint32_t *)smem);
+        return;
+    }
+    if (blockIdx.x == wa.chk_n) {                       // ... and one for the table's end
+        if (wa.tail_chunk) ix_check_chunk(a, (a.ix_K - 1) / a.ix_per_chunk, (uint32_t *)smem);
+        if (threadIdx.x == 0) ix_tail_check(a);
+        return;
+    }
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));    // (wave uniform: what follows from it stays in scalar registers)
+    F::contig(a, wa.w, a.status, smem, wave, (blockIdx.x - wa.chk_n - 1) * 4 + wave, WinSrcContig());
+}
+// a batch: the window found in the descriptor array, a status word per window
+template <class F>
+__global__ void __launch_bounds__(256, F::waves) win_batch_kernel(const WinBatchArgs ba) {
+    const DecArgs &a = ba.d;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    if (blockIdx.x < ba.chk_n) {                        // the launch's first workgroups: a chunk of the container's table each
+        ix_check_chunk(a, ba.chunks[blockIdx.x], (uint32_t *)smem);
+        return;
+    }
+    if (blockIdx.x < ba.chk_n + ba.tail) {              // ... and one for the table's end
+        if (threadIdx.x == 0) ix_tail_check(a);
+        return;
+    }
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t gw = (blockIdx.x - ba.chk_n - ba.tail) * 4 + wave;
+    const uint32_t i = win_search(ba.wins, ba.nwin, gw);
+    const WinDesc w = ba.wins[i];                       // sixteen dwords, read before anything is stored
+    F::contig(a, w, ba.wstatus + i, smem, wave, gw - w.wave0, WinSrcContig());
+}
+// a batch from pieces: no check workgroups (the host verified the chunks before a byte of the stream was asked for)
+template <class F>
+__global__ void __launch_bounds__(256, F::waves) win_ranged_kernel(const WinRangedArgs ra) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t gw = blockIdx.x * 4 + wave;
+    const uint32_t i = win_search(ra.wins, ra.nwin, gw);
+    const WinDesc w = ra.wins[i];
+    F::pieces(ra.d, w, ra.wstatus + i, smem, wave, gw - w.wave0, ra.src);
+}
+template <class F> inline void win_launch(F, const WinArgs &wa, const WinLaunch &l) {
+    hipLaunchKernelGGL((win_one_kernel<F>), dim3(l.grid), dim3(256), l.lds, (hipStream_t)l.stream, wa);
+}
+template <class F> inline void win_launch(F, const WinBatchArgs &ba, const WinLaunch &l) {
+    hipLaunchKernelGGL((win_batch_kernel<F>), dim3(l.grid), dim3(256), l.lds, (hipStream_t)l.stream, ba);
+}
+template <class F> inline void win_launch(F, const WinRangedArgs &ra, const WinLaunch &l) {
+    hipLaunchKernelGGL((win_ranged_kernel<F>), dim3(l.grid), dim3(256), l.lds, (hipStream_t)l.stream, ra);
+}
+// for the picks: a band count and a band map as types
+template <int N> using WinInt = std::integral_constant<int, N>;
+// for the records: destinations on any address, on a value; the LDS of the families that bring dec_px_kernel's
+inline uint32_t window_align_any(const Geometry &) { return 1; }
+inline uint32_t window_align_value(const Geometry &g) { return g.tsz; }
+inline size_t window_lds_px(const Geometry &, const DecPlan &plan) { return plan.lds_px; }
 
 // Wave `wid` of window w (wave: its number in the workgroup of four; both wave uniform): the k-th segment of one of the window's block
 // rows, decoded as dec_px_kernel's BL branch does, stored where the window's blocks go.  status: the word this window's failures go to.
@@ -332,5 +402,33 @@ __device__ __forceinline__ void win_decode_wave(const DecArgs &a, const WinDesc 
         else if (a.in_bits - used > 7) atomicOr(status, 2u);
     }
 }
+
+// The 8-bit family's instantiations (k_dec_win.hip, k_dec_wins.hip, k_dec_wins_ranged.hip), by the raster's bands, the plan's band
+// map, the raster's order and mode
+template <int B, bool RGB, uint64_t ORDER, bool STEP>
+struct WinU8 {
+    static constexpr int waves = 0;
+    static constexpr auto contig = &win_decode_wave<B, RGB, ORDER, STEP, WinSrcContig>;
+    static constexpr auto pieces = &win_decode_wave<B, RGB, ORDER, STEP, WinSrcPieces>;
+};
+template <class Visit>
+inline void win_u8_pick(const Geometry &g, const DecPlan &plan, Visit visit) {
+    const bool step = g.mode != CM_FTL, z = g.order == ZCURVE;
+    auto go = [&](auto bc, auto rgbc) {
+        constexpr int B = decltype(bc)::value;
+        constexpr bool RGB = decltype(rgbc)::value;
+        if (!z && !step) visit(WinU8<B, RGB, HILBERT, false>());
+        else if (!z && step) visit(WinU8<B, RGB, HILBERT, true>());
+        else if (z && !step) visit(WinU8<B, RGB, ZCURVE, false>());
+        else visit(WinU8<B, RGB, ZCURVE, true>());
+    };
+    if (g.bands == 1) go(WinInt<1>(), std::false_type());
+    else if (g.bands == 3) { if (plan.px_rgb) go(WinInt<3>(), std::true_type()); else go(WinInt<3>(), std::false_type()); }
+    else { if (plan.px_rgb) go(WinInt<4>(), std::true_type()); else go(WinInt<4>(), std::false_type()); }
+}
+// ... and its dispatchers, one a file
+void win_u8_one(const Geometry &g, const DecPlan &plan, const WinArgs &wa, const WinLaunch &l);
+void win_u8_batch(const Geometry &g, const DecPlan &plan, const WinBatchArgs &ba, const WinLaunch &l);
+void win_u8_ranged(const Geometry &g, const DecPlan &plan, const WinRangedArgs &ra, const WinLaunch &l);
 
 }  // namespace qb3dev

@@ -258,27 +258,35 @@ __device__ __forceinline__ void win16_decode_wave(const DecArgs &a, const WinDes
     }
 }
 
-// What the launchers of the 16-bit window kernels share (k_dec_win16.hip, k_dec_wins16_ranged.hip).
-// one place names the instantiations: KERNEL<BG, RGB, ORDER, STEP> by the plan's bands per lane and band map, the raster's order and mode
-#define QB3_WIN16_DISPATCH(KERNEL, args)                                                                                              \
-    do {                                                                                                                              \
-        const bool step = g.mode != CM_FTL, z = g.order == ZCURVE;                                                                    \
-        auto go = [&](auto bgc, auto rgbc) {                                                                                          \
-            constexpr int BG = decltype(bgc)::value;                                                                                  \
-            constexpr bool RGB = decltype(rgbc)::value;                                                                               \
-            if (!z && !step) hipLaunchKernelGGL((KERNEL<BG, RGB, HILBERT, false>), grid, dim3(256), plan.lds_px, st, args);           \
-            else if (!z && step) hipLaunchKernelGGL((KERNEL<BG, RGB, HILBERT, true>), grid, dim3(256), plan.lds_px, st, args);        \
-            else if (z && !step) hipLaunchKernelGGL((KERNEL<BG, RGB, ZCURVE, false>), grid, dim3(256), plan.lds_px, st, args);        \
-            else hipLaunchKernelGGL((KERNEL<BG, RGB, ZCURVE, true>), grid, dim3(256), plan.lds_px, st, args);                         \
-        };                                                                                                                            \
-        using T = std::true_type; using F = std::false_type;                                                                          \
-        switch (plan.px16_bg) {                                                                                                       \
-        case 1: go(std::integral_constant<int, 1>(), F()); break;                                                                     \
-        case 2: go(std::integral_constant<int, 2>(), F()); break;                                                                     \
-        case 3: if (plan.px_rgb) go(std::integral_constant<int, 3>(), T()); else go(std::integral_constant<int, 3>(), F()); break;    \
-        default: if (plan.px_rgb) go(std::integral_constant<int, 4>(), T()); else go(std::integral_constant<int, 4>(), F()); break;   \
-        }                                                                                                                             \
-    } while (0)
+// The family's instantiations (k_dec_win16.hip, k_dec_wins16_ranged.hip), by the plan's bands per lane and band map, the raster's order
+// and mode; four waves a SIMD asked for
+template <int BG, bool RGB, uint64_t ORDER, bool STEP>
+struct Win16 {
+    static constexpr int waves = 4;
+    static constexpr auto contig = &win16_decode_wave<BG, RGB, ORDER, STEP, WinSrcContig>;
+    static constexpr auto pieces = &win16_decode_wave<BG, RGB, ORDER, STEP, WinSrcPieces>;
+};
+template <class Visit>
+inline void win16_pick(const Geometry &g, const DecPlan &plan, Visit visit) {
+    const bool step = g.mode != CM_FTL, z = g.order == ZCURVE;
+    auto go = [&](auto bgc, auto rgbc) {
+        constexpr int BG = decltype(bgc)::value;
+        constexpr bool RGB = decltype(rgbc)::value;
+        if (!z && !step) visit(Win16<BG, RGB, HILBERT, false>());
+        else if (!z && step) visit(Win16<BG, RGB, HILBERT, true>());
+        else if (z && !step) visit(Win16<BG, RGB, ZCURVE, false>());
+        else visit(Win16<BG, RGB, ZCURVE, true>());
+    };
+    using T = std::true_type; using F = std::false_type;
+    switch (plan.px16_bg) {
+    case 1: go(WinInt<1>(), F()); break;
+    case 2: go(WinInt<2>(), F()); break;
+    case 3: if (plan.px_rgb) go(WinInt<3>(), T()); else go(WinInt<3>(), F()); break;
+    default: if (plan.px_rgb) go(WinInt<4>(), T()); else go(WinInt<4>(), F()); break;
+    }
+}
+
+void win16_ranged(const Geometry &g, const DecPlan &plan, const WinRangedArgs &ra, const WinLaunch &l);      // (k_dec_wins16_ranged.hip)
 
 inline void window16_dec_args(DecArgs &a, const DecPlan &plan) {       // what dec_px16_kernel's lanes take besides window_dec_args
     a.px_ng = plan.px16_ng; a.px_magic_ng = magic_div(a.px_ng); a.in_cap_full = plan.px_cap_dw;

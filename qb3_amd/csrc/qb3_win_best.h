@@ -239,21 +239,29 @@ __device__ __forceinline__ void win_best_decode_wave(const DecArgs &a, const Win
     }
 }
 
-// one place names the instantiations: KERNEL<B, RGB, ORDER> by the raster's bands, the plan's band map and the raster's order
-#define QB3_WIN_BEST_DISPATCH(KERNEL, args)                                                                                           \
-    do {                                                                                                                              \
-        auto go = [&](auto bc, auto rgbc) {                                                                                           \
-            constexpr int B = decltype(bc)::value;                                                                                    \
-            constexpr bool RGB = decltype(rgbc)::value;                                                                               \
-            if (g.order == ZCURVE) hipLaunchKernelGGL((KERNEL<B, RGB, ZCURVE>), grid, dim3(256), plan.lds_px, st, args);              \
-            else hipLaunchKernelGGL((KERNEL<B, RGB, HILBERT>), grid, dim3(256), plan.lds_px, st, args);                               \
-        };                                                                                                                            \
-        using T = std::true_type; using F = std::false_type;                                                                          \
-        switch (g.bands) {                                                                                                            \
-        case 1: go(std::integral_constant<int, 1>(), F()); break;                                                                     \
-        case 3: if (plan.px_rgb) go(std::integral_constant<int, 3>(), T()); else go(std::integral_constant<int, 3>(), F()); break;    \
-        default: if (plan.px_rgb) go(std::integral_constant<int, 4>(), T()); else go(std::integral_constant<int, 4>(), F()); break;   \
-        }                                                                                                                             \
-    } while (0)
+// The family's instantiations (k_dec_win_best.hip, k_dec_wins_best_ranged.hip), by the raster's bands, the plan's band map and the
+// raster's order
+template <int B, bool RGB, uint64_t ORDER>
+struct WinCf8 {
+    static constexpr int waves = win_best_waves(B);
+    static constexpr auto contig = &win_best_decode_wave<B, RGB, ORDER, WinSrcContig>;
+    static constexpr auto pieces = &win_best_decode_wave<B, RGB, ORDER, WinSrcPieces>;
+};
+template <class Visit>
+inline void win_cf8_pick(const Geometry &g, const DecPlan &plan, Visit visit) {
+    auto go = [&](auto bc, auto rgbc) {
+        constexpr int B = decltype(bc)::value;
+        constexpr bool RGB = decltype(rgbc)::value;
+        if (g.order == ZCURVE) visit(WinCf8<B, RGB, ZCURVE>());
+        else visit(WinCf8<B, RGB, HILBERT>());
+    };
+    using T = std::true_type; using F = std::false_type;
+    switch (g.bands) {
+    case 1: go(WinInt<1>(), F()); break;
+    case 3: if (plan.px_rgb) go(WinInt<3>(), T()); else go(WinInt<3>(), F()); break;
+    default: if (plan.px_rgb) go(WinInt<4>(), T()); else go(WinInt<4>(), F()); break;
+    }
+}
+void win_cf8_ranged(const Geometry &g, const DecPlan &plan, const WinRangedArgs &ra, const WinLaunch &l);    // (k_dec_wins_best_ranged.hip)
 
 }  // namespace qb3dev

@@ -111,4 +111,21 @@ __device__ __forceinline__ void winu_best_decode_wave(const DecArgs &a, const Wi
 // the launch's LDS: four waves' worst-case staging (or, where that is larger, their tiles); no code table
 inline size_t window_best_unit_lds_bytes(const Geometry &g, const DecPlan &plan) { return 4 * (size_t)pxu_wave_bytes(plan.px_cap_dw, g.tsz); }
 
+// The family's instantiations (k_dec_win_best_unit.hip), by the raster's value size
+template <typename T>
+struct WinCfu {
+    static constexpr int waves = 0;
+    static constexpr auto contig = &winu_best_decode_wave<T, WinSrcContig>;
+    static constexpr auto pieces = &winu_best_decode_wave<T, WinSrcPieces>;
+};
+template <class Visit>
+inline void win_cfu_pick(const Geometry &g, const DecPlan &, Visit visit) {
+    switch (g.tsz) {
+    case 1: visit(WinCfu<uint8_t>()); break;
+    case 2: visit(WinCfu<uint16_t>()); break;
+    case 4: visit(WinCfu<uint32_t>()); break;
+    default: visit(WinCfu<uint64_t>()); break;
+    }
+}
+
 }  // namespace qb3dev

@@ -204,4 +204,27 @@ inline void window_unit_dec_args(DecArgs &a, const DecPlan &plan) {
 // the launch's LDS: the code table and four waves' worst-case staging (or, where that is larger, their tiles)
 inline size_t window_unit_lds_bytes(const Geometry &g, const DecPlan &plan) { return 2048 + 4 * (size_t)pxu_wave_bytes(plan.px_cap_dw, g.tsz); }
 
+// The family's instantiations (k_dec_win_unit.hip), by the raster's value size and mode
+template <typename T, bool STEP>
+struct WinUnit {
+    static constexpr int waves = 0;
+    static constexpr auto contig = &winu_decode_wave<T, STEP, WinSrcContig>;
+    static constexpr auto pieces = &winu_decode_wave<T, STEP, WinSrcPieces>;
+};
+template <class Visit>
+inline void win_unit_pick(const Geometry &g, const DecPlan &, Visit visit) {
+    const bool step = g.mode != CM_FTL;
+    auto go = [&](auto t) {
+        typedef decltype(t) T;
+        if (step) visit(WinUnit<T, true>());
+        else visit(WinUnit<T, false>());
+    };
+    switch (g.tsz) {
+    case 1: go(uint8_t()); break;
+    case 2: go(uint16_t()); break;
+    case 4: go(uint32_t()); break;
+    default: go(uint64_t()); break;
+    }
+}
+
 }  // namespace qb3dev
