@@ -124,7 +124,7 @@ __global__ void __launch_bounds__(256) dec_px_kernel(const DecArgs a0) {
     bool bad = !fits;
     const uint32_t binc = wave_iscan32(blen);           // inclusive: lane 63 holds the bits of the segment
     // rung switches of the lane's units
-    uint32_t gpos[B], pos = cpos + binc - blen, dpk[NW];
+    uint32_t gpos[B], swb[B], pos = cpos + binc - blen, dpk[NW];     // (swb: what each band's switch left of its 32 bits, kept across the scan)
     uint32_t rp[B][8], spk[NW], sinc[NW];
 #pragma unroll
     for (int k = 0; k < NW; k++) { dpk[k] = 0; spk[k] = 0; }
@@ -135,12 +135,12 @@ __global__ void __launch_bounds__(256) dec_px_kernel(const DecArgs a0) {
 #pragma unroll
         for (int c = 0; c < B; c++) {
             pos = pos < limit ? pos : limit;
-            bool sig; uint32_t csl;
-            const uint32_t d = px_switch(pos, &csl, &sig);
+            bool sig; uint32_t csl, sw;
+            const uint32_t d = px_switch(pos, &csl, &sig, &sw);
             if (act && sig && STEP) bad = true;         // common-factor / index unit: not handled here
             const uint32_t rung = (rg0[c] + wave_iscan32(act ? d : 0u)) & 7u;
             uint32_t end;
-            const uint32_t tot = px_group<STEP>(pos + csl, rung, rp[c], &end) & 0xffu;
+            const uint32_t tot = px_group<STEP, true>(pos + csl, rung, rp[c], &end, sw) & 0xffu;
             spk[c >> 1] |= (act ? tot : 0u) << (16 * (c & 1));
             pos = end;
         }
@@ -150,7 +150,7 @@ __global__ void __launch_bounds__(256) dec_px_kernel(const DecArgs a0) {
         for (int c = 0; c < B; c++) {
             pos = pos < limit ? pos : limit;
             bool sig; uint32_t csl;
-            const uint32_t d = px_switch(pos, &csl, &sig);
+            const uint32_t d = px_switch(pos, &csl, &sig, &swb[c]);
             gpos[c] = pos + csl;
             if (act && sig && STEP) bad = true;         // common-factor / index unit: not handled here
             dpk[c >> 1] |= (act ? d : 0u) << (16 * (c & 1));
@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(256) dec_px_kernel(const DecArgs a0) {
 #pragma unroll
         for (int c = 0; c < B; c++) {
             const uint32_t rung = (rg0[c] + ((dpk[c >> 1] >> (16 * (c & 1))) & 0xffffu)) & 7u;
-            const uint32_t tot = px_group<STEP>(gpos[c], rung, rp[c]) & 0xffu;
+            const uint32_t tot = px_group<STEP, true>(gpos[c], rung, rp[c], nullptr, swb[c]) & 0xffu;
             spk[c >> 1] |= (act ? tot : 0u) << (16 * (c & 1));
         }
     }

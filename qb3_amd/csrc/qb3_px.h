@@ -172,17 +172,19 @@ constexpr PxDecTab make_px_dec_tab() {
 }
 static __device__ const PxDecTab px_dec_tab = make_px_dec_tab();
 
-// rung switch of an 8-bit unit at bit `pos`: delta (mod 8); *cslen = bits consumed
-__device__ __forceinline__ uint32_t px_switch(uint32_t pos, uint32_t *cslen, bool *signal) {
-    uint32_t x = lds_bits(pos);
+// rung switch of an 8-bit unit at bit `pos`: delta (mod 8); *cslen = bits consumed (1, 3, 4 or 5); *rest = what is left of
+// the 32 bits read, the stream from pos + *cslen on: at least 27 valid bits, zeros above them (px_group decodes from it)
+__device__ __forceinline__ uint32_t px_switch(uint32_t pos, uint32_t *cslen, bool *signal, uint32_t *rest) {
+    const uint32_t x0 = lds_bits(pos);
     *signal = false;
-    if (!(x & 1)) { *cslen = 1; return 0; }
-    x >>= 1;                                            // code at rung 2 (reference QB3decode.h:97-116)
+    if (!(x0 & 1)) { *cslen = 1; *rest = x0 >> 1; return 0; }
+    const uint32_t x = x0 >> 1;                         // code at rung 2 (reference QB3decode.h:97-116)
     uint32_t m, len;
     if (!(x & 1)) { m = (x & 3) >> 1; len = 2; }
     else if (!(x & 2)) { m = ((x >> 2) & 1) | 2; len = 3; }
     else { m = ((x >> 2) & 3) | 4; len = 4; }
     *cslen = 1 + len;
+    *rest = x >> len;
     if (m == 6) { *signal = true; return 0; }
     return (m & 1) ? (8 - (m + 1) / 2) & 7 : m / 2 + 1;
 }
@@ -190,11 +192,23 @@ __device__ __forceinline__ uint32_t px_switch(uint32_t pos, uint32_t *cslen, boo
 // the 16 values of an 8-bit unit whose codes start at bit `gpos`: rp[k] = running sums of values 2k, 2k+1 as two
 // 16-bit lanes (low byte = the sum mod 256); returns the unit total (garbage above bit 7)
 // (*end, when asked for: the bit behind the unit)
-template <bool STEP>
-__device__ __forceinline__ uint32_t px_group(uint32_t gpos, uint32_t rung, uint32_t (&rp)[8], uint32_t *end = nullptr) {
+// A refill (lds_bits: a paired LDS read and a funnel shift) is a dependent round trip in the chain pos -> bits -> length -> pos, so
+// there are as few as the code lengths allow.  A code is rung, rung + 1 or rung + 2 bits: at most 8 up to rung 6, 9 at rung 7.
+//   CARRY: `carry` is what px_switch left of its 32 bits, the stream from gpos on.  The switch took at most 5 bits, so 32 - 5 = 27
+//     valid ones are left: 27 >= 3 x 9 serves codes 0, 1, 2 at every rung, and 27 >= 17 the whole rung-0 form.  From code 3 on there
+//     is a refill every FOUR codes (3, 7, 11, 15: 32 >= 4 x 8), and the lanes at rung 7 refill once more before the fourth code of a
+//     group (6, 10, 14: 36 > 32) -- one masked read under the per-unit predicate, which a wave without a rung-7 lane jumps over.  One
+//     code path for the sixteen values: the lanes of a wave sit at different rungs.  Reads a unit, the switch's included: 5 at rungs 1
+//     to 6 (7 before), 1 at rung 0 (2 before), 8 at rung 7 (7 before).
+//   without (the 16-bit kernels, for their units below rung 8; the four-band window kernel without the step): the position only, a
+//     refill every three codes (32 >= 3 x 9), six a unit.  The four-code cadence was built for these callers too (refills before codes
+//     0, 4, 8, 12, at rung 7 also before 3, 7, 11, 15) and not kept: DESIGN, "8-bit decoders: five bit refills a unit".
+template <bool STEP, bool CARRY = false>
+__device__ __forceinline__ uint32_t px_group(uint32_t gpos, uint32_t rung, uint32_t (&rp)[8], uint32_t *end = nullptr, uint32_t carry = 0) {
+    constexpr int FIRST = CARRY ? 3 : 0, PER = CARRY ? 4 : 3;      // codes in front of the first refill, codes a refill
     uint32_t acc = 0;
     if (rung == 0) {
-        const uint32_t x = lds_bits(gpos);
+        const uint32_t x = CARRY ? carry : lds_bits(gpos);
         const uint32_t bits = (x & 1) ? (x >> 1) & 0xffffu : 0u;
         if (end) *end = gpos + ((x & 1) ? 17 : 1);
 #pragma unroll
@@ -206,10 +220,12 @@ __device__ __forceinline__ uint32_t px_group(uint32_t gpos, uint32_t rung, uint3
     }
     const uint32_t base = 16u << rung, m2 = base - 4;   // table region and the mask of (rung+2 bits) << 2
     const uint32_t K = rung * 0x11111111u + 0x20102010u; // code length by the low three bits, 4 bits each
-    uint32_t pos = gpos, buf = 0, fl = 0;
+    const bool nine = rung == 7;
+    uint32_t pos = gpos, buf = carry, fl = 0;
 #pragma unroll
     for (int i = 0; i < 16; i++) {
-        if (i % 3 == 0) buf = lds_bits(pos);            // three codes are at most 27 bits
+        if (i >= FIRST && (i - FIRST) % PER == 0) buf = lds_bits(pos);                          // the refill of a group of PER codes
+        else if (PER == 4 && i > FIRST && (i - FIRST) % 4 == 3 && nine) buf = lds_bits(pos);   // rung 7: again before the group's fourth
         const uint32_t t = buf << 2;
         const uint32_t e = *lds_at((t & m2) | base);
         const uint32_t len = __builtin_amdgcn_ubfe(K, t, 4);

@@ -306,15 +306,18 @@ __device__ __forceinline__ void win_decode_wave(const DecArgs &a, const WinDesc 
     // band after band: the switch, the band's rungs across the segment (a scan of the switches), the unit, and where it
     // ended is where the next band's unit starts
     const uint32_t blk_end = pos + blen;
+    // (the unit decodes from what the switch left of its bits -- not with four bands and no step: that kernel takes 72 registers
+    // with it, 7 waves a SIMD, and 64 without)
+    constexpr bool CARRY = B != 4 || STEP;
 #pragma unroll
     for (int c = 0; c < B; c++) {
         pos = pos < limit ? pos : limit;
-        bool sig; uint32_t csl;
-        const uint32_t d = px_switch(pos, &csl, &sig);
+        bool sig; uint32_t csl, sw;
+        const uint32_t d = px_switch(pos, &csl, &sig, &sw);
         if (act && sig && STEP) bad = true;             // common-factor / index unit: not handled here
         const uint32_t rung = (rg0[c] + wave_iscan32(act ? d : 0u)) & 7u;
         uint32_t end;
-        const uint32_t tot = px_group<STEP>(pos + csl, rung, rp[c], &end) & 0xffu;
+        const uint32_t tot = px_group<STEP, CARRY>(pos + csl, rung, rp[c], &end, sw) & 0xffu;
         spk[c >> 1] |= (act ? tot : 0u) << (16 * (c & 1));
         pos = end;
     }

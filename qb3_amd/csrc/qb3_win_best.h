@@ -114,14 +114,14 @@ __device__ __forceinline__ void win_best_decode_wave(const DecArgs &a, const Win
     for (int c = 0; c < B; c++) {
         if (pos > limit) { pos = limit; clamped = true; }       // (a table's length that leads behind what was staged: the unit reads zeros)
         const uint32_t oldrung = (bt >> (16 + 4 * c)) & 7u;
-        bool sig; uint32_t csl;
-        const uint32_t d = px_switch(pos, &csl, &sig);
+        bool sig; uint32_t csl, sw;
+        const uint32_t d = px_switch(pos, &csl, &sig, &sw);
         uint32_t rung = (oldrung + d) & 7u, end = pos, tot = 0;
         uint8_t g[16];
         uint32_t kind = 3, cfv = 0;
         const bool slow = act && sig;
         if (slow) { if (!best_slow_unit(pos + csl, oldrung, g, &kind, &cfv, &rung, &end)) bad = true; }
-        else tot = px_group<true>(pos + csl, rung, rp[c], &end) & 0xffu;
+        else tot = px_group<true, true>(pos + csl, rung, rp[c], &end, sw) & 0xffu;
         if (__any(slow)) {
             // the factor in force: the nearest lane below with a unit that brought its own, else the segment entry's
             const uint64_t wm = __ballot(slow && kind == 0);
