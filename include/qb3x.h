@@ -282,8 +282,22 @@ size_t qb3x_decoder_table_entries(const decsp p);
  * relied on the table fails -- decodes the stream WITHOUT the table (the plain walk: what the reference, which skips the
  * chunk, does).  A damaged table costs time, never pixels.  An entry: 6-byte little-endian bit position of its first unit
  * (from the first stream bit), a rung byte per band, the value entering each band (the type's width, little-endian),
- * and with flag bit 0 the common factor entering each band likewise.  Entry k starts at block k * (blocks per entry);
- * every chunk but the last holds the same number of entries.  The reference's decoder steps over them
+ * and with flag bit 0 the common factor entering each band likewise.  The rung byte is the rung the band's first unit is entered
+ * with (the one the unit before left; 0 in entry 0), also where the entry's fields say it again.  The entering value is the
+ * band-differenced one (the band map's, modulo the type's width) of the pixel the curve visits last in the block before, 0 in
+ * entry 0.  The factor is the band-state value the reference keeps (QB3common.h:63-65): the factor of the band's last
+ * common-factor unit MINUS 2, 0 before the first such unit -- not the factor itself.  Entry k starts at block k * (blocks per entry);
+ * every chunk but the last holds the same number of entries, (65535 - 12) / (bytes an entry) of them, rounded down.  The head's
+ * blocks-per-entry word is the raster's blocks per index segment in every table this library writes, also where the decoder
+ * derives it from the raster: 64 for 8-bit rasters of 1 / 3 / 4 bands and for one band of any width, in every mode; FTL / BASE
+ * streams of 16-bit rasters: 64 for 2, 3 and 4 bands, 21 for six, 32 for eight, 12 for ten, 21 for twelve, 9 for fourteen, 16 for
+ * sixteen (64 / lanes a block, a lane owning four bands where the count is a multiple of four, else two); 64 / bands, rounded down,
+ * for every other raster -- the common-factor streams of several 16-bit bands among them.  Every field of a block or unit behind the raster's last is
+ * zero, and so are the bits of an entry's last byte behind its last field (an odd number of twelve-bit fields): a table is a function
+ * of the stream and the raster's shape alone -- not of the level where two levels have the same layout, of the call that wrote it
+ * (host, device, tile batch, reindex), of the out-of-band index being asked for, or of what the destination held.
+ * tests/qb3_table_spec.py states all of this in numpy and is what the encoder's bytes are compared with.
+ * The reference's decoder steps over them
  * (QB3decode.cpp:251-255) and decodes the same pixels: it skips an unknown chunk by its length field counted from the
  * chunk START, so the field holds the whole chunk size, and the pad makes the container parse the same for a reader
  * that adds the 4 head bytes to it.  This library's decoder uses the table when no out-of-band index is given:
@@ -302,8 +316,9 @@ size_t qb3x_decoder_table_entries(const decsp p);
  * 0.7 %.  The decoder then needs neither a walk nor an index -- one kernel, twice the decode rate from the container alone
  * (16384 x 16384 x 3: 0.37 ms instead of 0.65).  16-bit rasters of 2, 3, 4, 6 or 8 bands (FTL/BASE): an entry (one per 64 lanes of
  * the decoder's wave; a lane owns up to four bands of a block) ends with two fields per lane -- four bands: the bit lengths of the
- * band PAIRS (0,1) and (2,3); three: of (0,1) and of band 2; two: of each band -- ten bits each, 160 bytes -- about 5 % of a typical stream (8192 x 8192 x 8: 0.65 ms instead of 0.94); 16-bit rasters of ONE band:
- * a field per block (its unit's length), 80 bytes an entry.  32/64-bit rasters
+ * band PAIRS (0,1) and (2,3); three: of (0,1) and of band 2; two: of each band; six: three lanes a block of two bands each, a field a band, 21 blocks an entry, both fields of lane 63 zero; eight: two lanes a block of four bands each, their pairs; lanes block-major, a block's lanes in band order -- ten bits each, 160 bytes -- about 5 % of a typical stream (8192 x 8192 x 8: 0.65 ms instead of 0.94); 16-bit rasters of ONE band:
+ * a field per block (its unit's length), 80 bytes an entry; 16-bit rasters of an even band count ABOVE eight (10, 12, 14, 16): no
+ * length fields, flag bit 1 clear -- their level-2 table is their level-1 table.  32/64-bit rasters
  * (FTL/BASE, where the unit-parallel decoder applies): an entry ends with a twelve-bit length per UNIT of its segment
  * (band-minor, little endian) -- about 10 % of a stream of small units (4096 x 4096 int32: 0.06 ms instead of 0.40).
  * Every OTHER FTL/BASE raster (8-bit data of 2 or more than 4 bands, 16-bit data of an odd band count above 4, 32/64-bit data of
@@ -318,7 +333,10 @@ size_t qb3x_decoder_table_entries(const decsp p);
  * decodes from the container alone in 0.47 ms (round 2: 2.4 ms).  Every other common-factor stream (several bands; round 4):
  * at either level an entry per segment of 64 / bands blocks that ends with a three-byte field per UNIT (band-minor): the
  * unit's bits (12) | the rung it is entered with << 12 -- what the lane-per-unit decoder works from (8192 x 8192 x 8 uint16
- * in QB3M_CF_H from the container alone: 1.0 ms; 2.3 before). */
+ * in QB3M_CF_H from the container alone: 1.0 ms; 2.3 before).  So every common-factor table this library writes carries fields
+ * (flags 3) and is the same at level 1 and level 2; entries without fields in a common-factor table (one per about 64 units) are
+ * what earlier versions wrote: still read, no longer written.  In the one-band fields the rung takes six bits (bits 12..17), in the
+ * per-unit fields likewise; the bits above are zero. */
 void qb3x_set_encoder_index_chunk(encsp p, int on);
 
 /* Reindex: a restart table for a container that exists -- a file the reference or GDAL wrote, one of this library's with a table of

@@ -9,6 +9,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import qb3_spec as S  # noqa: E402
+from qb3_table_spec import oracle_units  # noqa: E402
 
 FTL, BASE = 8, 4
 WIDTHS = {1: 0, 2: 2, 4: 4, 8: 6}            # bytes -> unsigned QB3 type
@@ -147,23 +148,6 @@ def test_spec_writes_the_oracles_units(oracle, nbytes, mode):
         assert dec == (g if max(g) > 1 else [v & 1 for v in g]), (r, pos)
         old = r
     assert pos == nbits
-
-
-def oracle_units(oracle, img, dtype, mode):
-    """(stream int, bits, trace rows) of the oracle's raw unit stream of a 4n x 4 x 1 raster; a trace row: start bit, kind (N plain,
-    0 rung 0, C common factor, I index), rung of the deltas, factor, factor before"""
-    import ctypes as C
-    import tempfile
-    lib = oracle.lib
-    lib.qb3o_set_trace.argtypes, lib.qb3o_set_trace.restype = [C.c_char_p], None
-    with tempfile.NamedTemporaryFile("r", suffix=".txt") as f:
-        lib.qb3o_set_trace(f.name.encode())
-        try:
-            bits, n = oracle_raw_bits(oracle, img, dtype, mode)
-        finally:
-            lib.qb3o_set_trace(None)
-        rows = [ln.split() for ln in f.read().splitlines()]
-    return bits, n, [(int(a), k, int(r), int(c), int(p)) for a, k, r, c, p in rows]
 
 
 @pytest.mark.parametrize("nbytes", [1, 2, 4, 8])

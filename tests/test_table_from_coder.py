@@ -1,13 +1,21 @@
 """Level-2 restart tables of the 8-bit lane-per-block FTL/BASE coder (k_enc_px.hip): the coding kernel writes the entries, the
 concatenation launch their stream positions, chunk heads and checks.  Every table here is checked byte for byte against one
-rebuilt in numpy from the out-of-band index of the same encode (layout: qb3_dev.h, IndexView; table: IxTable, include/qb3x.h)."""
+rebuilt from the out-of-band index of the same encode (layout: qb3_dev.h, IndexView) -- the coder agrees with itself -- and against
+the one tests/qb3_table_spec.py builds from the CPU oracle's unit trace and the pixels -- and with a truth that is not its own.  The
+entry packing, the chunk heads and the check are the spec module's (include/qb3x.h in numpy), stated there once."""
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import qb3_table_spec as T  # noqa: E402
+from qb3_table_spec import table_span  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 FTL, BASE = 8, 4
-IX_HEAD = 12
 
 
 def _a8(v):
@@ -15,57 +23,25 @@ def _a8(v):
 
 
 def rebuild_table(index, w, h, b):
-    """the level-2 table (an entry per 64-block segment: position, rungs, entering values, sixteen groups of four ten-bit block
-    lengths), its chunks with heads, pads and checks, and the closing "DT", from the index of an 8-bit raster of b bands"""
+    """the level-2 table (an entry per 64-block segment: position, rungs, entering values, a ten-bit length per block), its chunks
+    with heads, pads and checks, and the closing "DT", from the index of an 8-bit raster of b bands"""
     index = np.asarray(index, np.uint8)
     nblocks = ((w + 3) // 4) * ((h + 3) // 4)
     nseg = (nblocks + 63) // 64
     off = 0
-    bitpos = np.frombuffer(index[:8 * nseg].tobytes(), "<u8")
+    t = T.Table()
+    t.lay = T.layout(0, b, FTL, 2)
+    t.pos = np.frombuffer(index[:8 * nseg].tobytes(), "<u8")
     off += _a8(8 * nseg)
-    prev = index[off:off + nseg * b].reshape(nseg, b)
+    t.prev = index[off:off + nseg * b].reshape(nseg, b).astype(np.uint64)
     off += 2 * _a8(nseg * b)                            # entering values, then the factors (none in FTL / BASE)
-    rung = index[off:off + nseg * b].reshape(nseg, b)
+    t.rungs = index[off:off + nseg * b].reshape(nseg, b)
     off += _a8(nseg * b)
-    ulen = index[off:off + nblocks * b].reshape(nblocks, b).astype(np.uint64)
-    bl = np.zeros(nseg * 64, np.uint64)
+    ulen = index[off:off + nblocks * b].reshape(nblocks, b).astype(np.int64)
+    bl = np.zeros(nseg * 64, np.int64)
     bl[:nblocks] = ulen.sum(1)
-    g = bl.reshape(nseg, 16, 4)
-    packed = g[:, :, 0] | g[:, :, 1] << np.uint64(10) | g[:, :, 2] << np.uint64(20) | g[:, :, 3] << np.uint64(30)
-    lens = ((packed[:, :, None] >> (np.uint64(8) * np.arange(5, dtype=np.uint64))) & np.uint64(255)).astype(np.uint8).reshape(nseg, 80)
-    pos = ((bitpos[:, None] >> (np.uint64(8) * np.arange(6, dtype=np.uint64))) & np.uint64(255)).astype(np.uint8)
-    entries = np.concatenate([pos, rung, prev, lens], axis=1)
-    E = entries.shape[1]
-    per_chunk = (65535 - IX_HEAD) // E
-    out = []
-    for c0 in range(0, nseg, per_chunk):
-        body = entries[c0:c0 + per_chunk].reshape(-1)
-        i = np.arange(len(body), dtype=np.uint64)
-        s = int(((body.astype(np.uint64) + np.uint64(1)) * ((i * np.uint64(0x9E3779B1) + np.uint64(1)) & np.uint64(0xFFFFFFFF))).sum()) & 0xFFFFFFFF
-        f = (s ^ (s >> 16)) & 0xFFFF
-        ln = IX_HEAD + len(body)
-        head = bytes([ord("i"), ord("x"), ln & 255, ln >> 8, 3, 2, f & 255, f >> 8]) + (64).to_bytes(4, "little")
-        out.append(head + body.tobytes() + b"zz\x04\x00")
-    return b"".join(out) + b"DT"
-
-
-def table_span(c):
-    """[start, end) of a container's table chunks, "DT" included"""
-    pos, t0 = 11, None
-    c = bytes(c)
-    while pos + 4 <= len(c):
-        sig, ln = c[pos:pos + 2], c[pos + 2] | c[pos + 3] << 8
-        if sig == b"DT":
-            assert t0 is not None, "no table"
-            return t0, pos + 2
-        if sig in (b"ix", b"zz"):
-            t0 = pos if t0 is None else t0
-            pos += ln
-        elif sig in (b"CB", b"QV", b"SC"):
-            pos += 4 + ln
-        else:
-            raise AssertionError("unexpected chunk %r at %d" % (sig, pos))
-    raise AssertionError("no DT")
+    t.cf, t.fields = None, bl.reshape(nseg, 64)
+    return T.assemble(t)
 
 
 def check_container(oracle, host, index, img_host, w, h, b, mode):
@@ -76,6 +52,9 @@ def check_container(oracle, host, index, img_host, w, h, b, mode):
     if got != want:
         d = next(i for i in range(len(got)) if got[i] != want[i])
         raise AssertionError("table differs from the index's at byte %d of %d" % (d, len(got)))
+    img = np.ascontiguousarray(img_host).reshape(h, w, b)
+    spec_bytes, spec = T.build(T.units(oracle, img, 0, mode), T.entering_values(img, 0), 0, mode, 2)
+    assert T.compare(bytes(host), spec_bytes, spec, 0, mode) == (t0, t1)
     ref = oracle.encode(img_host, 0, mode)
     dt_at = bytes(ref).index(b"DT", 11)
     assert t0 == dt_at
