@@ -30,9 +30,8 @@ __global__ void __launch_bounds__(256) dec_px_kernel(const DecArgs a0) {
     const uint64_t stride = a.g.stride;
 
     uint32_t *tab = (uint32_t *)smem;                   // 4 KB, at LDS address 0 (the table addressing relies on it)
-    uint32_t *stage = tab + 1024 + wave * (a.in_cap_dw + 8);
+    const uint32_t stage_dw = 1024 + wave * (a.in_cap_dw + 8);       // the wave's staging: in_cap_dw + 8 dwords from here on
     const uint32_t lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t *)smem;
-    const uint32_t stage_bit0 = 8 * (lds0 + (uint32_t)((uint8_t *)stage - smem));
     // Two dependent round trips lie in front of the decoding, "entry, then stream words", and a wave spends a large part of its life
     // in them.  The first is made of the loads that depend on nothing but the segment number: the thread's sixteen bytes of the code
     // table, the position, the next segment's position, rungs and entering values, the lane's length(s).  All of them are
@@ -85,6 +84,39 @@ __global__ void __launch_bounds__(256) dec_px_kernel(const DecArgs a0) {
     const uint32_t ndw = fits ? (uint32_t)ndw64 : 0;
     const uint64_t left = endw_abs > w0 ? endw_abs - w0 : 0;
     const uint32_t lim = left < ndw ? (uint32_t)left : ndw;          // the words of them the stream has: the rest are staged as zeros
+    // Sixteen bytes a lane and load wherever the four-word groups of the segment all lie in front of the stream's last word (wave
+    // uniform; every segment but the stream's last few): two loads in flight per lane from in32 + w0 + 4 * (lane + 64 k) -- dword
+    // aligned, which is all a global load asks for; w0 is not aligned down, so no word is read that the dword loop of another wave would
+    // not read -- then two 16-byte LDS stores at the same index.  Those need the staging to start at a multiple of 16 bytes: where the
+    // wave's does not (in_cap_dw is no multiple of four: four bands) the segment is staged `pad` dwords further on, which all but a
+    // segment of the worst-case length have room for.  A lane past the segment's groups loads the last of them; words at or behind ndw
+    // are stored as zeros, the groups up to the one that holds word ndw + 7 are written (`lastg`: it must end inside the wave's staging),
+    // and a lane past those stores that group's zeros again.
+    const uint32_t nd4 = (ndw + 3) & ~3u, lastg = (ndw + 7) & ~3u, pad = (0u - stage_dw) & 3u;
+    const bool by16 = ndw != 0 && w0 + nd4 < endw_abs && pad + lastg + 4 <= a.in_cap_dw + 8;
+    uint32_t *stage = tab + stage_dw + (by16 ? pad : 0u);
+    const uint32_t stage_bit0 = 8 * (lds0 + (uint32_t)((uint8_t *)stage - smem));
+    if (by16) {
+        typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+        const uint8_t *src = (const uint8_t *)(a.in32 + w0);     // (the wave's: a lane adds a 32-bit byte offset)
+#pragma unroll 1
+        for (uint32_t base = 0; base < ndw + 8; base += 512) {  // (one round but for segments above 504 words)
+            uint4 sq[2];
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const uint32_t i = base + 4 * (lane + 64 * k);
+                const u32x4_a4 v = *(const u32x4_a4 *)(src + 4 * (i < nd4 - 4 ? i : nd4 - 4));
+                sq[k] = make_uint4(v.x, v.y, v.z, v.w);
+            }
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const uint32_t i = base + 4 * (lane + 64 * k);
+                const uint4 z = make_uint4(i < ndw ? sq[k].x : 0u, i + 1 < ndw ? sq[k].y : 0u, i + 2 < ndw ? sq[k].z : 0u, i + 3 < ndw ? sq[k].w : 0u);
+                *(uint4 *)(stage + (i < lastg ? i : lastg)) = z;
+            }
+        }
+    } else
+    // The stream's end, a truncated stream, a segment that does not fit: a dword a lane and load, clamped.
     // Eight loads in flight per lane, then eight LDS stores, neither with a branch between them: a lane past the segment's words loads
     // the last of them and stores a zero; 8 zero words follow the staged ones, and a lane past those stores the last zero again.  A
     // segment without a word in the stream loads nothing (`lim` is the wave's: one jump round all eight).
