@@ -176,6 +176,38 @@ size_t qb3x_read_windows(decsp p, const qb3x_window *wins, size_t n);
 int    qb3x_window_ok(const decsp p, size_t i);     /* 1: window i of the last batch call was written */
 int    qb3x_window_path(const decsp p, size_t i);   /* 0 failed, 1 / 2 / 3 as qb3x_last_window_path */
 
+/* Band-selected windows: the batch calls above with CHOSEN BANDS of every pixel in place of all of them -- three of eight for a false-
+ * colour composite, the bands a model was trained on, one band for an index map.  sel is a HOST array of nsel band numbers,
+ * 1 <= nsel <= 16, each below the raster's band count; any order, and a band may appear more than once.
+ * Bytes: window i receives h rows of w * nsel values; value k of pixel (x, y) is band sel[k] of that pixel as
+ * qb3x_decode_windows_device writes it -- the crop of the whole decode with the bands picked, for every container and handle setting
+ * (compat flags, quanta, band map, scan order; dequantisation is elementwise, so it commutes with the selection).  dst_stride is in
+ * values, 0 meaning w * nsel; no byte outside the h runs of w * nsel values is written.  Returns the number of windows written.
+ * qb3x_window_ok, qb3x_window_path, qb3x_last_window_path, qb3x_last_window_segments and qb3x_last_decode_status mean what they mean
+ * after qb3x_decode_windows_device; the three paths and "a damaged table costs time, never pixels, window by window" hold unchanged.
+ * Errors are decided before anything is launched or written (QB3E_EINV, 0 returned): everything the batch call refuses, with
+ * w * nsel in the stride rule, and sel == NULL, nsel == 0, nsel > 16, a band number at or above the raster's band count.
+ * The identity selection (nsel == bands, sel[k] == k) IS qb3x_decode_windows_device / qb3x_read_windows: same code, same launches.
+ * Two routes give the bytes:
+ *   fused   rasters of QB3X_WINK_UNIT / QB3X_WINK_CFU on a handle that set the bit, d_index == NULL, the table the family needs,
+ *           every destination on a multiple of the value size and (blocks of a segment) * nsel <= 64 (always so for nsel <= bands):
+ *           the family's window kernel writes the selected bands itself -- nothing else runs, and nsel / bands of the bytes are
+ *           written (profile names dec_window_unit, dec_window_best_unit);
+ *   gather  every other case: the full-band pixels are produced as for qb3x_decode_windows_device, into memory the handle owns (path
+ *           1: tight windows written by the family's kernel, sized by the windows; paths 2 and 3: the scratch raster), and ONE launch
+ *           per path picks the bands into the destinations, which may lie at any address (profile name win_band_gather).  At most
+ *           two such launches a call: one for the windows a shortcut gave, one for those the whole decode gave.  The call then waits
+ *           for `stream`.
+ * qb3x_last_window_gathers: gather launches of the handle's last band-selected call -- 0 when every window's pixels came straight
+ * from a window kernel, and 0 for the identity selection. */
+size_t qb3x_decode_windows_bands_device(decsp p, const void *d_src, const void *d_index, const qb3x_window *wins, size_t n,
+                                        const uint8_t *sel, size_t nsel, void *stream);
+/* The same for a container in HOST memory and host destinations: STORED containers are cropped and selected on the host without a
+ * device; else the container goes up ONCE and only the selected bands of the windows come down.  A handle over the container's head
+ * only (qb3x_read_start, qb3x_open_ranged) is refused (QB3E_EINV), as by qb3x_read_windows. */
+size_t qb3x_read_windows_bands(decsp p, const qb3x_window *wins, size_t n, const uint8_t *sel, size_t nsel);
+size_t qb3x_last_window_gathers(const decsp p);
+
 /* Ranged window reads: windows of a container the caller does NOT hold in memory -- a file, an object in a store -- fetching only the
  * bytes that hold the rectangles.  The caller gives a reader: rd(ctx, offset, dst, size) copies `size` container bytes from `offset`
  * to dst (host memory) and returns 0, or nonzero on failure; it is called from the calling thread only, one call at a time, and never
@@ -385,7 +417,7 @@ size_t qb3_decode(decsp p, void *destination);                                  
  * events on the launch stream; totals are resolved at the library's own synchronisation points.
  * Kernel names: enc_units, enc_scan, enc_concat, enc_seams, enc_best_units, enc_best_scan, enc_best_recode,
  * dec_index_table, dec_index_serial, dec_index_prev, dec_index_scan, dec_units, dec_segments, dec_window (the window kernel of
- * qb3x_decode_window_device, path 1), dec_window16 (the 16-bit window kernels: path 1 under QB3X_WINK_U16), dec_window_best (the window kernels of the 8-bit common-factor modes: path 1 under QB3X_WINK_CF8), dec_window_unit (the window kernels of the lane-per-unit and one-band 32/64-bit rasters: path 1 under QB3X_WINK_UNIT), dec_window_best_unit (those of the common-factor streams of such shapes: path 1 under QB3X_WINK_CFU), dec_window_ranged (the same from fetched pieces: the ranged calls), dec_window16_ranged (... of 16-bit rasters under QB3X_WINK_U16), dec_window_best_ranged (... of 8-bit common-factor rasters under QB3X_WINK_CF8), reindex_fill, reindex_finish (qb3x_reindex_device: the table's entries; everything else of the
+ * qb3x_decode_window_device, path 1), dec_window16 (the 16-bit window kernels: path 1 under QB3X_WINK_U16), dec_window_best (the window kernels of the 8-bit common-factor modes: path 1 under QB3X_WINK_CF8), dec_window_unit (the window kernels of the lane-per-unit and one-band 32/64-bit rasters: path 1 under QB3X_WINK_UNIT), dec_window_best_unit (those of the common-factor streams of such shapes: path 1 under QB3X_WINK_CFU), dec_window_ranged (the same from fetched pieces: the ranged calls), dec_window16_ranged (... of 16-bit rasters under QB3X_WINK_U16), dec_window_best_ranged (... of 8-bit common-factor rasters under QB3X_WINK_CF8), win_band_gather (the band pick of the band-selected window calls where no window kernel writes the selection itself), reindex_fill, reindex_finish (qb3x_reindex_device: the table's entries; everything else of the
  * new container).
  * level: 0 off, 1 every kernel, 2 all but the microsecond kernels (enc_scan, enc_seams, enc_best_scan), whose two
  * events cost more than they take. */

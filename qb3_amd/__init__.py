@@ -105,6 +105,9 @@ _PROTOS = {
     "qb3x_read_windows": (_sz, [_vp, _vp, _sz]),
     "qb3x_window_ok": (C.c_int, [_vp, _sz]),
     "qb3x_window_path": (C.c_int, [_vp, _sz]),
+    "qb3x_decode_windows_bands_device": (_sz, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "qb3x_read_windows_bands": (_sz, [_vp, _vp, _sz, _vp, _sz]),
+    "qb3x_last_window_gathers": (_sz, [_vp]),
     "qb3x_open_ranged": (_vp, [_vp, _vp, _u64, C.POINTER(_sz)]),
     "qb3x_read_windows_ranged": (_sz, [_vp, _vp, _sz]),
     "qb3x_decode_windows_ranged": (_sz, [_vp, _vp, _sz, _vp]),
@@ -234,9 +237,18 @@ def decode_window(stream, x0, y0, w, h, compat=0):
         lib.qb3_destroy_decoder(p)
 
 
-def decode_windows(stream, rects, compat=0):
+def band_array(bands):
+    """the `sel` array of the band-selected window calls (uint8 band numbers) from a sequence of ints"""
+    bands = [int(b) for b in bands]
+    if any(b < 0 or b > 255 for b in bands):
+        raise ValueError("band numbers are 0 .. 255")
+    return (C.c_uint8 * len(bands))(*bands)
+
+
+def decode_windows(stream, rects, compat=0, bands=None):
     """qb3_read_start .. qb3x_read_windows: the windows (x0, y0, w, h) of `rects` of a container in host memory -- one upload, one
-    decode call -- as a list of arrays of shape (h, w, bands) and the raster's type."""
+    decode call -- as a list of arrays of shape (h, w, bands) and the raster's type.  bands: a sequence of band numbers (any order,
+    repeats allowed, 1 to 16 of them): qb3x_read_windows_bands, arrays of shape (h, w, len(bands)) that hold those bands only."""
     import numpy as np
     buf = np.ascontiguousarray(stream, dtype=np.uint8)
     dims = (_sz * 3)()
@@ -249,11 +261,14 @@ def decode_windows(stream, rects, compat=0):
         if compat:
             lib.qb3x_set_decoder_compat(p, compat)
         rects = [tuple(int(v) for v in r) for r in rects]
-        outs = [np.empty((h, w, dims[2]), dtype=NP_DTYPE[lib.qb3_get_type(p)]) for _, _, w, h in rects]
+        outs = [np.empty((h, w, dims[2] if bands is None else len(bands)), dtype=NP_DTYPE[lib.qb3_get_type(p)]) for _, _, w, h in rects]
         wins = window_array(rects, [o.ctypes.data for o in outs])
-        n = lib.qb3x_read_windows(p, wins, len(rects))
+        if bands is None:
+            n = lib.qb3x_read_windows(p, wins, len(rects))
+        else:
+            n = lib.qb3x_read_windows_bands(p, wins, len(rects), band_array(bands), len(bands))
         if n != len(rects):
-            raise RuntimeError(f"qb3x_read_windows wrote {n} of {len(rects)} windows: {last_error()}")
+            raise RuntimeError(f"qb3x_read_windows{'' if bands is None else '_bands'} wrote {n} of {len(rects)} windows: {last_error()}")
         return outs
     finally:
         lib.qb3_destroy_decoder(p)

@@ -45,8 +45,8 @@ static bool window_crop(decsp p, const void *d_raster, const qb3x_window &w, hip
 }
 
 // a container in device memory as the kernels take it: geometry and plan, the container's table, the stream's first bit and its length
-struct WinSrc { Geometry g; DecPlan plan; IxTable ixt; const uint32_t *in32; uint32_t in_bit0; uint64_t in_bits; };
-static WinSrc window_source(const decs *p, const Geometry &g, const void *d_src) {
+// (struct WinSrc: qb3_host.h)
+WinSrc qb3api::window_source(const decs *p, const Geometry &g, const void *d_src) {
     const size_t off = (size_t)(p->s_in - p->s_start);
     return WinSrc{ g, plan_decode(g), handle_table(p, (const uint8_t *)d_src + p->ix_off), (const uint32_t *)((const uint8_t *)d_src + (off & ~(size_t)3)),
                    (uint32_t)(8 * (off & 3)), (uint64_t)p->s_size * 8 };
@@ -65,8 +65,11 @@ static bool window_kernel_one(decsp p, const WinSrc &s, const qb3x_window &w, ui
     return true;
 }
 // path 1, a batch: descriptors and the chunk list are built in the pinned area, one copy up; n + 1 status words, one memset, one copy back
-static bool window_kernel_batch(decsp p, const WinSrc &s, const qb3x_window *wins, size_t n, uint8_t *paths, size_t *segs, hipStream_t st, const WinKernels &fam) {
-    const size_t dbytes = n * WIN_DESC_BYTES, upbytes = dbytes + 4 * ix_chunks(s.ixt), stbytes = 4 * (n + 1);
+// (ws: a band-selected call -- the family's band-selected form when ws->sel is set, and ws->extra_bytes more bytes behind the chunk list, on sixteen)
+bool qb3api::window_kernel_batch(decsp p, const WinSrc &s, const qb3x_window *wins, size_t n, uint8_t *paths, size_t *segs, hipStream_t st, const WinKernels &fam,
+                                 const WinSel *ws) {
+    const size_t dbytes = n * WIN_DESC_BYTES, extra = ws ? ws->extra_bytes : 0;
+    const size_t upbytes = dbytes + 4 * ix_chunks(s.ixt) + (extra ? 16 + extra : 0), stbytes = 4 * (n + 1);
     if (!p->h_wdesc.ensure(upbytes) || !p->h_wst.ensure(stbytes) || !p->d_wdesc.ensure(upbytes) || !p->d_wst.ensure(stbytes)) return false;
     std::vector<WinRect> rects(n);
     std::vector<void *> dsts(n);
@@ -76,10 +79,18 @@ static bool window_kernel_batch(decsp p, const WinSrc &s, const qb3x_window *win
     const size_t nchunks = window_batch_plan(s.g, s.ixt, rects.data(), dsts.data(), n, p->h_wdesc.p, chunks, &wsegs);
     if (nchunks) memcpy((uint8_t *)p->h_wdesc.p + dbytes, chunks.data(), 4 * nchunks);
     uint32_t *d_status = (uint32_t *)p->d_wst.p;
-    HIPOK(hipMemcpyAsync(p->d_wdesc.p, p->h_wdesc.p, dbytes + 4 * nchunks, hipMemcpyHostToDevice, st));
+    size_t up = dbytes + 4 * nchunks;
+    if (extra) {
+        up = (up + 15) & ~(size_t)15;
+        memcpy((uint8_t *)p->h_wdesc.p + up, ws->extra, extra);
+        *ws->d_extra = (const uint8_t *)p->d_wdesc.p + up;
+        up += extra;
+    }
+    HIPOK(hipMemcpyAsync(p->d_wdesc.p, p->h_wdesc.p, up, hipMemcpyHostToDevice, st));
     if (hipMemsetAsync(d_status, 0, stbytes, st) != hipSuccess) return false;
     if (launch_decode_windows(fam, s.g, s.plan, s.in32, s.in_bit0, s.in_bits, p->h_wdesc.p, p->d_wdesc.p, n,
-                              (const uint32_t *)((const uint8_t *)p->d_wdesc.p + dbytes), nchunks, d_status, st, s.ixt)) return false;
+                              (const uint32_t *)((const uint8_t *)p->d_wdesc.p + dbytes), nchunks, d_status, st, s.ixt,
+                              ws ? ws->sel : nullptr, ws ? ws->nsel : 0)) return false;
     hipError_t e = hipMemcpyAsync(p->h_wst.p, d_status, stbytes, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = wait_stream(st);
     if (e != hipSuccess) { set_error("window batch kernel", (int)e); return false; }
@@ -90,7 +101,8 @@ static bool window_kernel_batch(decsp p, const WinSrc &s, const qb3x_window *win
     return true;
 }
 // path 2: the segments of the windows' block rows into the scratch raster, one status word for all of them, then the crops
-static bool window_strips(decsp p, const WinSrc &s, const qb3x_window *wins, size_t n, uint8_t *paths, size_t *segs, hipStream_t st) {
+// (crop false: a band-selected call, whose gather reads the scratch raster)
+bool qb3api::window_strips(decsp p, const WinSrc &s, const qb3x_window *wins, size_t n, uint8_t *paths, size_t *segs, hipStream_t st, bool crop) {
     const Geometry &g = s.g;
     if (!p->d_win.ensure(qb3_decoded_size(p)) || !p->d_ws.ensure(s.plan.ws_bytes)) return false;
     std::vector<std::pair<uint64_t, uint64_t>> rg(n);
@@ -110,7 +122,7 @@ static bool window_strips(decsp p, const WinSrc &s, const qb3x_window *wins, siz
     const hipError_t e = fetch_small(&status, d_status, 4, st);
     if (e != hipSuccess) { set_error("window strips", (int)e); return false; }
     for (size_t i = 0; i < n && !status; i++) {
-        if (!window_crop(p, p->d_win.p, wins[i], st)) return false;
+        if (crop && !window_crop(p, p->d_win.p, wins[i], st)) return false;
         paths[i] = 2;
     }
     return true;

@@ -11,6 +11,10 @@ static void win_cfu_one(const Geometry &g, const DecPlan &plan, const WinArgs &w
 static void win_cfu_batch(const Geometry &g, const DecPlan &plan, const WinBatchArgs &ba, const WinLaunch &l) {
     win_cfu_pick(g, plan, [&](auto f) { win_launch(f, ba, l); });
 }
+// the band-selected batch: the same wave routine with winu_store_tile's SEL (ba.d.sel_nibs, ba.d.nsel)
+static void win_cfu_batch_sel(const Geometry &g, const DecPlan &plan, const WinBatchArgs &ba, const WinLaunch &l) {
+    win_cfu_pick<true>(g, plan, [&](auto f) { win_launch(f, ba, l); });
+}
 
 static bool decode_window_best_unit_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix) {
     const DecKernel k = aligned_dec_kernel(g, plan);
@@ -36,7 +40,7 @@ static bool decode_window_best_unit_ok(const Geometry &g, const DecPlan &plan, c
 //     detected by neither this kernel nor the whole decode from the table: both give the same wrong pixels.
 // Destinations must be value aligned: the stores are winu_store_tile's.
 const WinKernels &win_cfu() {      // (in a function: host data, not for the device side of this file)
-    static const WinKernels k = { decode_window_best_unit_ok, QB3X_WINK_CFU, window_align_value, window_unit_dec_args, window_best_unit_lds_bytes, "common-factor lane-per-unit ", "dec_window_best_unit", nullptr, win_cfu_one, win_cfu_batch, nullptr };
+    static const WinKernels k = { decode_window_best_unit_ok, QB3X_WINK_CFU, window_align_value, window_unit_dec_args, window_best_unit_lds_bytes, "common-factor lane-per-unit ", "dec_window_best_unit", nullptr, win_cfu_one, win_cfu_batch, nullptr, win_cfu_batch_sel };
     return k;
 }
 

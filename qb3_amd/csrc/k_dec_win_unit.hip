@@ -10,6 +10,10 @@ static void win_unit_one(const Geometry &g, const DecPlan &plan, const WinArgs &
 static void win_unit_batch(const Geometry &g, const DecPlan &plan, const WinBatchArgs &ba, const WinLaunch &l) {
     win_unit_pick(g, plan, [&](auto f) { win_launch(f, ba, l); });
 }
+// the band-selected batch: the same wave routine with winu_store_tile's SEL (ba.d.sel_nibs, ba.d.nsel)
+static void win_unit_batch_sel(const Geometry &g, const DecPlan &plan, const WinBatchArgs &ba, const WinLaunch &l) {
+    win_unit_pick<true>(g, plan, [&](auto f) { win_launch(f, ba, l); });
+}
 
 static bool decode_window_unit_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix) {
     const DecKernel k = aligned_dec_kernel(g, plan);
@@ -32,7 +36,7 @@ static bool decode_window_unit_ok(const Geometry &g, const DecPlan &plan, const 
 //     mask -- so every destination must be value aligned.  A lane finds the numbers of the block it stores for (offset in the window,
 //     row and column masks) by a shuffle from the lane of that block's number.
 const WinKernels &win_unit() {      // (in a function: host data, not for the device side of this file)
-    static const WinKernels k = { decode_window_unit_ok, QB3X_WINK_UNIT, window_align_value, window_unit_dec_args, window_unit_lds_bytes, "lane-per-unit ", "dec_window_unit", nullptr, win_unit_one, win_unit_batch, nullptr };
+    static const WinKernels k = { decode_window_unit_ok, QB3X_WINK_UNIT, window_align_value, window_unit_dec_args, window_unit_lds_bytes, "lane-per-unit ", "dec_window_unit", nullptr, win_unit_one, win_unit_batch, nullptr, win_unit_batch_sel };
     return k;
 }
 

@@ -88,18 +88,19 @@ int launch_decode_window(const WinKernels &k, const Geometry &g, const DecPlan &
 
 int launch_decode_windows(const WinKernels &k, const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
                           const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
-                          uint32_t *d_status, void *stream, const IxTable &ix) {
+                          uint32_t *d_status, void *stream, const IxTable &ix, const uint8_t *sel, uint32_t nsel) {
     hipStream_t st = (hipStream_t)stream;
-    if (!k.ok(g, plan, ix) || !n) return window_refused(k, "window batch");
+    if (!k.ok(g, plan, ix) || !n || (sel && (!nsel || nsel > (uint32_t)MAXBANDS || !window_sel_fused(&k, g, nsel)))) return window_refused(k, "window batch");
     WinBatchArgs ba = {};
     window_dec_args(ba.d, g, plan, in32, in_bit0, in_bits, d_status, ix);
     if (k.more_args) k.more_args(ba.d, plan);
+    if (sel) window_sel_dec_args(ba.d, sel, nsel);
     ba.chunks = d_chunks;
     // in front of the first launch's waves: a workgroup for every chunk of the list and one for the tail check
     window_launches(ba, h_descs, d_descs, n, d_status, (uint32_t)nchunks + 1, [&](uint32_t grid, bool head) {
         ba.chk_n = head ? (uint32_t)nchunks : 0; ba.tail = head ? 1 : 0;
         ProfScope ps(k.prof, st);
-        k.batch(g, plan, ba, WinLaunch{ grid, k.lds(g, plan), stream });
+        (sel ? k.batch_sel : k.batch)(g, plan, ba, WinLaunch{ grid, k.lds(g, plan), stream });
     });
     HIPCHK(hipGetLastError());
     return 0;

@@ -314,6 +314,7 @@ struct WinKernels {
     void (*one)(const Geometry &, const DecPlan &, const WinArgs &, const WinLaunch &);
     void (*batch)(const Geometry &, const DecPlan &, const WinBatchArgs &, const WinLaunch &);
     void (*ranged)(const Geometry &, const DecPlan &, const WinRangedArgs &, const WinLaunch &);    // null: the family has no ranged form
+    void (*batch_sel)(const Geometry &, const DecPlan &, const WinBatchArgs &, const WinLaunch &);  // the batch form that writes selected bands only (null: the family has none)
 };
 const WinKernels &win_u8(), &win_u16(), &win_cf8(), &win_unit(), &win_cfu();
 bool decode_window_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix);        // win_u8's predicate (k_dec_win.hip)
@@ -339,7 +340,19 @@ size_t window_batch_plan(const Geometry &g, const IxTable &ix, const WinRect *re
                          std::vector<uint32_t> &chunks, uint64_t *segments);
 int launch_decode_windows(const WinKernels &k, const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
                           const void *h_descs, const void *d_descs, size_t n, const uint32_t *d_chunks, size_t nchunks,
-                          uint32_t *d_status, void *stream, const IxTable &ix);
+                          uint32_t *d_status, void *stream, const IxTable &ix,
+                          const uint8_t *sel = nullptr, uint32_t nsel = 0);
+// (sel: the band-selected form of a family that has one (WinKernels::batch_sel; window_sel_fused says when it applies): a pixel of every
+// window is the nsel values of bands sel[0 .. nsel), the descriptors' strides count those.)
+// Band-selected windows (qb3x_decode_windows_bands_device).  The fused form writes the selection straight from the window kernel; every
+// other case decodes full-band pixels into memory of the handle's and picks the bands with win_band_gather_kernel (k_win_bands.hip):
+// a descriptor a window -- where its full-band pixels are (src: the first value of the window's first pixel; spitch: bytes between
+// its rows; sbands: values a source pixel), where the selected ones go (dst at any address, dstride bytes between rows) -- and ONE
+// launch for n of them.  quanta > 1: the values are multiplied back as launch_dequantize does it (dtype: the handle's qb3_dtype).
+struct WinGather { const void *src; uint64_t spitch; void *dst; uint64_t dstride; uint32_t w, h, sbands, pad_; };
+constexpr size_t WIN_GATHER_BYTES = 48;
+inline bool window_sel_fused(const WinKernels *k, const Geometry &g, uint32_t nsel) { return k && k->batch_sel && g.seg_blocks * nsel <= 64; }
+int launch_window_gather(const void *d_descs, size_t n, uint64_t max_rows, const uint8_t *sel, uint32_t nsel, int dtype, uint64_t quanta, void *stream);
 // The same from PIECES of the container (api_ranged.cpp fetches them), for a family that has the form: d_pieces: npieces >= 1 pieces
 // sorted by first segment, each a run of consecutive segments { seg0, nseg, ent0, word0, stream word of its first packed word (low,
 // high), nwords, 0 }; d_entries: the compact array of table entries (ix.entry_bytes each), nseg + 1 per piece from index ent0; d_words:

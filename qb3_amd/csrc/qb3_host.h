@@ -123,6 +123,9 @@ struct decs {
     DevBuf d_wdesc;                                    // a batch of windows: descriptors and the list of table chunks to check, as uploaded
     PinBuf h_wdesc, h_wst;                             // ... their pinned host copy (one copy up), and the status words (one copy back)
     std::vector<uint8_t> wins_path;                    // ... per window outcome of the last batch call (0: not written, else its path)
+    DevBuf d_wfull, d_wgat;                            // band-selected windows (api_window_bands.cpp): full-band windows a window kernel wrote for the gather; the gather's descriptors
+    PinBuf h_wgat;                                     // ... their pinned host copy
+    size_t win_gathers = 0;                            // ... gather launches of the last band-selected call (qb3x_last_window_gathers)
     Stager stager, stager2;                            // (stager2: the download ring of a pipelined host call)
     Pipe pipe;                                         // ... its streams and events
     // a ranged handle (qb3x_open_ranged, api_ranged.cpp): the caller's reader, the container's size, what the last call asked of the reader
@@ -196,6 +199,15 @@ bool windows_out(decsp p, const qb3x_window *wins, size_t n, std::vector<void *>
 bool window_dequantize(decsp p, const qb3dev::Geometry &g, void *dst, size_t w, size_t h, size_t stride, hipStream_t st);
 size_t windows_device(decsp p, const void *d_src, const void *d_index, const qb3x_window *wins, size_t n, uint8_t *paths, bool single, hipStream_t st);
 size_t windows_host(decsp p, const qb3x_window *wins, size_t n, uint8_t *paths, bool single);
+// ... and what the band-selected calls (api_window_bands.cpp) take from there: the container as the kernels take it, the batch of a family
+// (sel: its band-selected form, the rectangles' strides then count nsel values a pixel; extra: bytes that go up behind the descriptors and the
+// chunk list in the same copy, *d_extra: where they are then), the strips of path 2 (crop: into the windows; else only the scratch raster)
+struct WinSrc { qb3dev::Geometry g; qb3dev::DecPlan plan; qb3dev::IxTable ixt; const uint32_t *in32; uint32_t in_bit0; uint64_t in_bits; };
+WinSrc window_source(const decs *p, const qb3dev::Geometry &g, const void *d_src);
+struct WinSel { const uint8_t *sel; uint32_t nsel; const void *extra; size_t extra_bytes; const void **d_extra; };
+bool window_kernel_batch(decsp p, const WinSrc &s, const qb3x_window *wins, size_t n, uint8_t *paths, size_t *segs, hipStream_t st, const qb3dev::WinKernels &fam,
+                         const WinSel *ws = nullptr);
+bool window_strips(decsp p, const WinSrc &s, const qb3x_window *wins, size_t n, uint8_t *paths, size_t *segs, hipStream_t st, bool crop = true);
 
 // qb3_api.cpp
 qb3dev::Geometry make_geometry(size_t w, size_t h, size_t bands, int dtype, size_t stride, uint64_t order, int mode,

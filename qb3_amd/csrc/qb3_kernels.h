@@ -341,6 +341,10 @@ struct DecArgs {
     uint32_t ntiles;
     uint64_t ts_in, ts_img, ts_idx;
     const uint64_t *tile_bits;
+    // band-selected windows (the SEL instantiations of the lane-per-unit window kernels, qb3_win_unit.h; nobody else reads them):
+    // the band of output slot k in nibble k, the slots of a pixel (1..16), and x / nsel as fastdiv takes it
+    uint64_t sel_nibs;
+    uint32_t nsel, magic_nsel;
 };
 
 

@@ -52,6 +52,31 @@ __device__ __forceinline__ void pxu_tile_fill(T *tile, const T (&o)[16], bool ac
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// The same for a band-selected window: the tile holds S output slots a pixel ([row][block][x][slot], RP = blocks * 4 * S elements a pixel
+// row), slot k takes band (nibs >> 4k) & 15.  A lane writes its sixteen values to every slot that names its band -- the slots are a mask
+// it computes once and walks bit by bit -- and a lane whose band no slot names writes nothing.  blocks * S <= 64: the tile stays inside
+// pxu_wave_bytes.  Slots are one value apart, as bands are in pxu_tile_fill: the stores read the tile as rows of bytes, and a slot
+// stride with a gap would cost them their pieces; at most as many lanes as there write into one dword (fewer slots than bands: fewer).
+template <typename T>
+__device__ __forceinline__ void pxu_tile_fill_sel(T *tile, const T (&o)[16], bool act, uint32_t blk, uint32_t c, uint32_t S, uint64_t nibs, uint32_t RP, uint64_t order) {
+    uint32_t slots = 0;
+    for (uint32_t k = 0; k < S; k++) slots |= (((uint32_t)(nibs >> (4 * k)) & 15u) == c) ? 1u << k : 0u;
+    if (!act) slots = 0;
+    while (slots) {
+        const uint32_t k = (uint32_t)__builtin_ctz(slots);
+        slots &= slots - 1;
+        const uint32_t e0 = blk * 4 * S + k;
+#pragma unroll
+        for (uint32_t i = 0; i < 16; i++) {
+            const uint32_t nib = curve_nib(order, i);
+            tile[e0 + (nib >> 2) * RP + (nib & 3) * S] = o[i];
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // bytes of LDS a wave needs: the staged words and, in their place afterwards, the tile; then a slot per block
 // (PXU_PAD zero words behind the staged ones: what wide_values_lds reads beyond a position inside the staged bits, qb3_wide.h)
 constexpr uint32_t PXU_PAD = WIDE_PAD_DW;

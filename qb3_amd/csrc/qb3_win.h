@@ -39,6 +39,12 @@ inline void window_desc(const Geometry &g, const WinRect &r, void *dst, WinDesc 
 // what a window kernel takes from the raster, the stream and the table (status: the word ix_check_chunk and ix_tail_check raise bits in)
 void window_dec_args(DecArgs &a, const Geometry &g, const DecPlan &plan, const uint32_t *in32, uint32_t in_bit0, uint64_t in_bits,
                      uint32_t *status, const IxTable &ix);
+// ... and the selection of a band-selected batch (sel: nsel band numbers, 1 <= nsel <= 16), for the SEL instantiations of qb3_win_unit.h
+inline void window_sel_dec_args(DecArgs &a, const uint8_t *sel, uint32_t nsel) {
+    a.sel_nibs = 0;
+    for (uint32_t k = 0; k < nsel; k++) a.sel_nibs |= (uint64_t)(sel[k] & 15u) << (4 * k);
+    a.nsel = nsel; a.magic_nsel = magic_div(nsel);
+}
 
 // what the single shell takes (win_one_kernel) ...
 struct WinArgs {

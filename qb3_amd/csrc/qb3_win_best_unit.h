@@ -14,7 +14,7 @@ namespace qb3dev {
 // waves and there is no workgroup barrier: a wave without a segment leaves at once.  T: the value as an unsigned number; the curve, the
 // band count and the band map are run-time values.  Every unit of the segment is parsed, whether the window holds its block or not: a
 // lane's entering value and factor come from the lanes below it.
-template <typename T, class SRC = WinSrcContig>
+template <typename T, class SRC = WinSrcContig, bool SEL = false>
 __device__ __forceinline__ void winu_best_decode_wave(const DecArgs &a, const WinDesc &w, uint32_t *status, uint8_t *smem, uint32_t wave, uint32_t wid, SRC src = SRC()) {
     constexpr uint32_t UB = UBits<T>::v, UMASK = (1u << UB) - 1;
     const uint32_t lane = threadIdx.x & 63;
@@ -97,7 +97,7 @@ __device__ __forceinline__ void winu_best_decode_wave(const DecArgs &a, const Wi
 #pragma unroll
         for (int i = 0; i < 16; i++) { const T v = pxu_shfl<T>(o[i], from); if (cb != c) o[i] = (T)(o[i] + v); }
     }
-    winu_store_tile<T>(a, w, wmem, o, act, blk, c, g0, nb_here);
+    winu_store_tile<T, SEL>(a, w, wmem, o, act, blk, c, g0, nb_here);
     if (bad) atomicOr(status, fits ? 1u : 8u);
     // a segment that reaches beyond the stream's end (a stream cut short): the whole-raster decode decides what its pixels are
     if (lane == 0 && (P1 > a.in_bits || P1 < P0)) atomicOr(status, 4u);
@@ -118,13 +118,23 @@ struct WinCfu {
     static constexpr auto contig = &winu_best_decode_wave<T, WinSrcContig>;
     static constexpr auto pieces = &winu_best_decode_wave<T, WinSrcPieces>;
 };
-template <class Visit>
+// ... and their band-selected variants (winu_store_tile's SEL): the batch form only
+template <typename T>
+struct WinCfuSel {
+    static constexpr int waves = 0;
+    static constexpr auto contig = &winu_best_decode_wave<T, WinSrcContig, true>;
+};
+template <bool SEL = false, class Visit>
 inline void win_cfu_pick(const Geometry &g, const DecPlan &, Visit visit) {
+    auto go = [&](auto t) {
+        typedef decltype(t) T;
+        if constexpr (SEL) visit(WinCfuSel<T>()); else visit(WinCfu<T>());
+    };
     switch (g.tsz) {
-    case 1: visit(WinCfu<uint8_t>()); break;
-    case 2: visit(WinCfu<uint16_t>()); break;
-    case 4: visit(WinCfu<uint32_t>()); break;
-    default: visit(WinCfu<uint64_t>()); break;
+    case 1: go(uint8_t()); break;
+    case 2: go(uint16_t()); break;
+    case 4: go(uint32_t()); break;
+    default: go(uint64_t()); break;
     }
 }
 

@@ -35,16 +35,20 @@ __device__ __forceinline__ void winu_store_whole(uint8_t *dst, const uint8_t *ti
 // band c): through the wave's LDS tile at wmem, which takes the place of the staged words; g0: the segment's first block, nb_here: its
 // blocks.  Whole blocks go row by row in pieces (winu_store_whole), edge blocks value by value under their column mask.  Both wave
 // routines call it: winu_decode_wave below and winu_best_decode_wave (qb3_win_best_unit.h).
-template <typename T>
+// SEL: a band-selected window (qb3x_decode_windows_bands_device): a pixel of the tile and of the window has a.nsel slots in place of the
+// raster's bands, slot k holds band (a.sel_nibs >> 4k) & 15 (pxu_tile_fill_sel); everything behind the fill runs with the slots for B.
+template <typename T, bool SEL = false>
 __device__ __forceinline__ void winu_store_tile(const DecArgs &a, const WinDesc &w, uint8_t *wmem, const T (&o)[16], bool act, uint32_t blk, uint32_t c,
                                                 uint32_t g0, uint32_t nb_here) {
-    const uint32_t lane = threadIdx.x & 63, NB = a.g.seg_blocks, nbx = a.g.nbx, B = a.g.bands;      // NB * B <= 64
+    const uint32_t lane = threadIdx.x & 63, NB = a.g.seg_blocks, nbx = a.g.nbx, B = SEL ? a.nsel : a.g.bands;      // NB * B <= 64
+    const uint32_t magic_B = SEL ? a.magic_nsel : a.magic_bands;
     // every lane holds its sixteen values in registers: the tile takes the place of the staged words
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     const uint32_t RP = NB * 4 * B;                     // tile elements per pixel row
-    pxu_tile_fill<T>((T *)wmem, o, act, blk, c, B, RP, a.g.order);
+    if constexpr (SEL) pxu_tile_fill_sel<T>((T *)wmem, o, act, blk, c, B, a.sel_nibs, RP, a.g.order);
+    else pxu_tile_fill<T>((T *)wmem, o, act, blk, c, B, RP, a.g.order);
 
     // lane L describes block L of the segment: is it one of the window's, which of its rows and columns are its own (a shifted last
     // block repeats pixels of its neighbour, which holds them by the rule) and inside the window, where its first pixel goes
@@ -75,7 +79,7 @@ __device__ __forceinline__ void winu_store_tile(const DecArgs &a, const WinDesc 
         const T *tile = (const T *)wmem;
         const uint32_t n = nb_here * 4 * B;
         for (uint32_t j0 = 0; j0 < n; j0 += 64) {
-            const uint32_t j = j0 + lane, eb = j / (4 * B), rem = j - eb * 4 * B, x = fastdiv(rem, B, a.magic_bands);
+            const uint32_t j = j0 + lane, eb = j / (4 * B), rem = j - eb * 4 * B, x = fastdiv(rem, B, magic_B);
             const uint32_t bi = pxu_shfl<uint32_t>(info, eb & 63u);
             const int64_t bo = (int64_t)pxu_shfl<uint64_t>((uint64_t)off, eb & 63u);
             if (j >= n || (bi & 0x100u) || !((bi >> (4 + x)) & 1u)) continue;
@@ -90,7 +94,7 @@ __device__ __forceinline__ void winu_store_tile(const DecArgs &a, const WinDesc 
 // Every wave of the workgroup comes here (there is one workgroup barrier); smem: the launch's dynamic LDS: the 2 KB code table, then
 // pxu_wave_bytes a wave, sized for the WORST-CASE segment (a.in_cap_dw = the plan's px_cap_dw): a segment that does not fit is not this
 // stream's (status bit 3).  T: the value as an unsigned number; the curve, the band count and the band map are run-time values.
-template <typename T, bool STEP, class SRC = WinSrcContig>
+template <typename T, bool STEP, class SRC = WinSrcContig, bool SEL = false>
 __device__ __forceinline__ void winu_decode_wave(const DecArgs &a, const WinDesc &w, uint32_t *status, uint8_t *smem, uint32_t wave, uint32_t wid, SRC src = SRC()) {
     constexpr uint32_t UB = UBits<T>::v, UMASK = (1u << UB) - 1;
     const uint32_t tid = threadIdx.x, lane = tid & 63;
@@ -186,7 +190,7 @@ __device__ __forceinline__ void winu_decode_wave(const DecArgs &a, const WinDesc
 #pragma unroll
         for (int i = 0; i < 16; i++) { const T v = pxu_shfl<T>(o[i], from); if (cb != c) o[i] = (T)(o[i] + v); }
     }
-    winu_store_tile<T>(a, w, wmem, o, act, blk, c, g0, nb_here);
+    winu_store_tile<T, SEL>(a, w, wmem, o, act, blk, c, g0, nb_here);
     if (bad) atomicOr(status, fits ? 1u : 8u);
     // a segment that reaches beyond the stream's end (a stream cut short): the whole-raster decode decides what its pixels are
     if (lane == 0 && (P1 > a.in_bits || P1 < P0)) atomicOr(status, 4u);
@@ -211,12 +215,19 @@ struct WinUnit {
     static constexpr auto contig = &winu_decode_wave<T, STEP, WinSrcContig>;
     static constexpr auto pieces = &winu_decode_wave<T, STEP, WinSrcPieces>;
 };
-template <class Visit>
+// ... and their band-selected variants: the batch form only (a.sel_nibs, a.nsel and a.magic_nsel are set)
+template <typename T, bool STEP>
+struct WinUnitSel {
+    static constexpr int waves = 0;
+    static constexpr auto contig = &winu_decode_wave<T, STEP, WinSrcContig, true>;
+};
+template <bool SEL = false, class Visit>
 inline void win_unit_pick(const Geometry &g, const DecPlan &, Visit visit) {
     const bool step = g.mode != CM_FTL;
     auto go = [&](auto t) {
         typedef decltype(t) T;
-        if (step) visit(WinUnit<T, true>());
+        if constexpr (SEL) { if (step) visit(WinUnitSel<T, true>()); else visit(WinUnitSel<T, false>()); }
+        else if (step) visit(WinUnit<T, true>());
         else visit(WinUnit<T, false>());
     };
     switch (g.tsz) {

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import lib, last_error, TYPESIZE, NP_DTYPE, QB3M_FTL, _sz, window_array, RangedReader
+from . import lib, last_error, TYPESIZE, NP_DTYPE, QB3M_FTL, _sz, window_array, band_array, RangedReader
 
 _vp = C.c_void_p
 
@@ -108,10 +108,13 @@ class DeviceDecoder:
             raise RuntimeError(f"qb3x_decode_device failed: {last_error()}")
         return out
 
-    def decode_window(self, d_stream, x0, y0, w, h, out=None, index=None):
+    def decode_window(self, d_stream, x0, y0, w, h, out=None, index=None, bands=None):
         """the w x h window at (x0, y0) of the raster (qb3x_decode_window_device): a device tensor of shape (h, w, bands) and the
-        raster's type.  out: a contiguous uint8 device tensor of at least the window's bytes to decode into."""
+        raster's type.  out: a contiguous uint8 device tensor of at least the window's bytes to decode into.  bands: as
+        decode_windows (a batch of one: qb3x_decode_windows_bands_device); the tensor's last dimension is len(bands)."""
         assert d_stream.is_cuda
+        if bands is not None:
+            return self.decode_windows(d_stream, [(x0, y0, w, h)], None if out is None else [out], index, bands)[0]
         dt = lib.qb3_get_type(self.p)
         nbytes = h * w * self.bands * TYPESIZE[dt]
         if out is None:
@@ -132,14 +135,17 @@ class DeviceDecoder:
         rasters, the same destinations; the bits may be or-ed; 0 (the default): none"""
         lib.qb3x_set_decoder_window_kernels(self.p, int(mask))
 
-    def decode_windows(self, d_stream, rects, out=None, index=None):
+    def decode_windows(self, d_stream, rects, out=None, index=None, bands=None):
         """the windows (x0, y0, w, h) of `rects` in ONE call (qb3x_decode_windows_device): a list of device tensors of shape
         (h, w, bands) and the raster's type.  out: a list of contiguous uint8 device tensors, one a window, of at least the
-        window's bytes each, to decode into (they may be views of one buffer; they must not overlap)."""
+        window's bytes each, to decode into (they may be views of one buffer; they must not overlap).  bands: a sequence of band
+        numbers (any order, repeats allowed, 1 to 16 of them): qb3x_decode_windows_bands_device, tensors of shape
+        (h, w, len(bands)) that hold those bands only; last_window_gathers() tells whether a window kernel wrote them itself."""
         assert d_stream.is_cuda
         dt = lib.qb3_get_type(self.p)
         rects = [tuple(int(v) for v in r) for r in rects]
-        sizes = [h * w * self.bands * TYPESIZE[dt] for _, _, w, h in rects]
+        nb_px = self.bands if bands is None else len(bands)
+        sizes = [h * w * nb_px * TYPESIZE[dt] for _, _, w, h in rects]
         if out is None:                 # one allocation, every window on a dword
             offs = [0]
             for nb in sizes:
@@ -150,12 +156,21 @@ class DeviceDecoder:
         for o, nb in zip(out, sizes):
             assert o.is_cuda and o.is_contiguous() and o.dtype == torch.uint8 and o.numel() >= nb
         wins = window_array(rects, [o.data_ptr() for o in out])
-        n = lib.qb3x_decode_windows_device(self.p, _vp(d_stream.data_ptr()), _vp(index.data_ptr()) if index is not None else None,
-                                           wins, len(rects), _stream_ptr())
+        d_index = _vp(index.data_ptr()) if index is not None else None
+        if bands is None:
+            n = lib.qb3x_decode_windows_device(self.p, _vp(d_stream.data_ptr()), d_index, wins, len(rects), _stream_ptr())
+        else:
+            n = lib.qb3x_decode_windows_bands_device(self.p, _vp(d_stream.data_ptr()), d_index, wins, len(rects), band_array(bands), len(bands),
+                                                     _stream_ptr())
         self._nwin = len(rects)
         if n != len(rects):
-            raise RuntimeError(f"qb3x_decode_windows_device wrote {n} of {len(rects)} windows: {last_error()}")
-        return [o.view(-1)[:nb].view(getattr(torch, NP_DTYPE[dt])).view(h, w, self.bands) for o, nb, (_, _, w, h) in zip(out, sizes, rects)]
+            raise RuntimeError(f"qb3x_decode_windows{'' if bands is None else '_bands'}_device wrote {n} of {len(rects)} windows: {last_error()}")
+        return [o.view(-1)[:nb].view(getattr(torch, NP_DTYPE[dt])).view(h, w, nb_px) for o, nb, (_, _, w, h) in zip(out, sizes, rects)]
+
+    def last_window_gathers(self):
+        """qb3x_last_window_gathers: gather launches of the last decode_windows(..., bands=...) -- 0: a window kernel wrote the selected
+        bands itself (or the selection was the identity)"""
+        return lib.qb3x_last_window_gathers(self.p)
 
     def reindex(self, d_stream, level, out=None):
         """the container with the restart table this library's encoder writes at `level` (0: none), its coded bytes untouched

@@ -39,6 +39,15 @@ the line also carries the kernel's own time (dec_window16_ranged, from the libra
 handles without the bit -- the file read whole, every call -- alternate with them in the same process, round by round (cold_off_ms,
 warm_off_ms and their bytes and reads beside cold_ms, warm_ms), and the kernel's own time is dec_window_best_ranged's.
 
+tools/window_bench.py [--kernels-unit | --kernels16] CASE --bands LIST -- band-selected windows (qb3x_decode_windows_bands_device, LIST: comma
+separated band numbers) against what a caller does without them, for batches of 64 windows of 256^2 and of 1024^2 at seeded origins, in
+one process, alternating over three rounds, events on the caller's stream: bands_ms, the band-selected call; full_ms, the full-band
+qb3x_decode_windows_device of the same windows on the same handle -- twice a round, so the line carries its own spread (full_spread_ms:
+the largest difference between the two of a round); full_pick_ms, that call followed by out[..., LIST].contiguous() in torch.  With
+--kernels-unit CASE is u8x5 / u16x7 / i32x1 / i64x2 and the lane-per-unit kernels write the selection themselves (gathers 0); with
+--kernels16 config3, or headline, full-band windows go to the handle's memory and one gather launch picks the bands (gathers 1).  The
+kernels' own times (the window kernel's and win_band_gather's) come from the library's profile in a pass of its own.
+
 tools/window_bench.py --write CASE FILE -- writes CASE's container (level-2 table) to FILE, for --ranged to read; CASE best is the
 container of bench.py's second configuration (16384 x 16384 x 3, QB3M_BEST)."""
 import json
@@ -195,6 +204,75 @@ def run_unit(case, cfu=False):
         print(json.dumps({"case": case, "mode": lib_mode(dec), **batch, "raster": [w, h, b], "bytes_per_value": tsz, "container_bytes": n, "window": [x0, y0, side, wh],
                           "path": last[1][0], "segments": last[1][1], "window_ms": t[1],
                           "path_off": last[0][0], "segments_off": last[0][1], "window_off_ms": t[0], "kernel_ms": kern}), flush=True)
+
+
+def run_bands(case, sel, kunit=False, kernels16=False):
+    """the band-selected batch against the full-band batch and against the full-band batch + a torch gather: see the head of the file"""
+    import numpy as np
+    import torch
+    from qb3_amd import synth, device as qdev, TYPESIZE, QB3X_WINK_U16, QB3X_WINK_UNIT
+    w, h, b, dt, gen = UNIT_CASES[case] if kunit else CASES[case][:5]
+    tsz, nsel = TYPESIZE[dt], len(sel)
+    img = synth.generate(w, h, b, dt, gen, 3)
+    raw = img.reshape(-1).view(torch.uint8)
+    enc = qdev.DeviceEncoder(w, h, b, dt, mode=8, want_index=False, index_chunk=2)
+    dst, n, _ = enc.encode(raw)
+    dec = qdev.DeviceDecoder(dst, n)
+    dec.set_window_kernels((QB3X_WINK_UNIT if kunit else 0) | (QB3X_WINK_U16 if kernels16 else 0))
+    kname = "dec_window_unit" if kunit else "dec_window16" if kernels16 else "dec_window"
+    tdt = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[tsz]      # (the value's width: torch indexes every signed type)
+    px = raw.view(tdt).view(h, w, b)
+    for side in (256, 1024):
+        rng = np.random.default_rng(64 + side)
+        rects = [(int(rng.integers(1, w - side)), int(rng.integers(1, h - side)), side, side) for _ in range(64)]
+        nb_full, nb_sel = side * side * b * tsz, side * side * nsel * tsz
+        full = torch.empty(64 * nb_full, dtype=torch.uint8, device="cuda")
+        part = torch.empty(64 * nb_sel, dtype=torch.uint8, device="cuda")
+        outs_full = [full[i * nb_full:(i + 1) * nb_full] for i in range(64)]
+        outs_sel = [part[i * nb_sel:(i + 1) * nb_sel] for i in range(64)]
+        full_px = full.view(tdt).view(64, side, side, b)
+        picked = []
+
+        def bands():
+            dec.decode_windows(dst, rects, out=outs_sel, bands=sel)
+
+        def whole():
+            dec.decode_windows(dst, rects, out=outs_full)
+
+        def whole_pick():
+            dec.decode_windows(dst, rects, out=outs_full)
+            picked[:] = [full_px[..., sel].contiguous()]
+
+        bands()
+        paths, gathers, segs = sorted(set(dec.last_windows)), dec.last_window_gathers(), dec.last_window[1]
+        whole_pick()
+        for i in (0, 1, 63):                            # the three ways give the source's pixels
+            x0, y0 = rects[i][:2]
+            want = px[y0:y0 + side, x0:x0 + side][:, :, sel]
+            assert torch.equal(part.view(tdt).view(64, side, side, nsel)[i], want), "band-selected bytes"
+            assert torch.equal(picked[0][i], want), "full-band bytes"
+        reps = 10 if side <= 256 else 3
+        t = {"bands": [], "full": [], "pick": []}
+        spread = 0.0
+        for _ in range(3):                              # alternating, three rounds; the full-band call twice a round
+            a = timed(whole, reps)
+            t["bands"].append(round(timed(bands, reps), 4))
+            t["pick"].append(round(timed(whole_pick, reps), 4))
+            c = timed(whole, reps)
+            t["full"] += [round(a, 4), round(c, 4)]
+            spread = max(spread, abs(a - c))
+        kern = {}
+        for fn in (bands, whole):
+            qdev.profile_reset()
+            qdev.profile_enable(1)
+            for _ in range(10):
+                fn()
+            torch.cuda.synchronize()
+            qdev.profile_enable(0)
+            kern[fn.__name__] = {k: round(v[0] / v[1], 4) for k, v in qdev.profile_report().items() if k in (kname, "win_band_gather")}
+        print(json.dumps({"case": case, "bands": sel, "raster": [w, h, b], "bytes_per_value": tsz, "windows": 64, "side": side, "paths": paths, "gathers": gathers,
+                          "segments": segs, "bands_ms": t["bands"], "full_ms": t["full"], "full_spread_ms": round(spread, 4), "full_pick_ms": t["pick"],
+                          "kernel_ms": kern}), flush=True)
 
 
 def lib_mode(dec):
@@ -358,7 +436,18 @@ if __name__ == "__main__":
     args = sys.argv[1:]
     k16, kcf, kunit, kcfu = "--kernels16" in args, "--kernels-cf" in args, "--kernels-unit" in args, "--kernels-cfu" in args
     args = [a for a in args if a not in ("--kernels16", "--kernels-cf", "--kernels-unit", "--kernels-cfu")]
-    if kcfu:
+    sel = None
+    if "--bands" in args:
+        at = args.index("--bands")
+        if at + 1 >= len(args):
+            sys.exit("window_bench: --bands takes a comma separated list of band numbers")
+        sel = [int(v) for v in args[at + 1].split(",")]
+        del args[at:at + 2]
+    if sel is not None:
+        if len(args) != 1 or args[0] not in (UNIT_CASES if kunit else CASES):
+            sys.exit("window_bench: --bands goes with one CASE (%s; with --kernels-unit: %s)" % (", ".join(CASES), ", ".join(UNIT_CASES)))
+        run_bands(args[0], sel, kunit, k16)
+    elif kcfu:
         if args[:1] != ["best"] or (len(args) > 1 and args[1] not in CFU_CASES):
             sys.exit("window_bench: --kernels-cfu goes with CASE best and, optionally, one of %s" % ", ".join(CFU_CASES))
         if len(args) > 1:
