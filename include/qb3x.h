@@ -284,6 +284,37 @@ size_t qb3x_decode_tiles(decsp p, const void *d_src, size_t n, size_t src_pitch,
                          void *d_dst, size_t dst_pitch, const void *d_index, void *stream);
 int qb3x_decode_tile_ok(const decsp p, size_t i);
 
+/* Mosaics: a W x H raster in device memory kept as a grid of independently coded tiles (the calling pattern of GDAL's MRF
+ * driver), coded from and decoded to the raster where it lies -- no copy into tile order.  The tile shape is the handle's
+ * (xsize x ysize = tw x th; tiles need not be square).  raster_stride is in values, 0 means W * bands; the handle's own
+ * qb3_set_*_stride setting is not used by these calls.
+ *
+ * qb3x_mosaic_tiles is pure geometry (no device): the tiles of the raster, tx = ceil(W / tw) a row, ty = ceil(H / th) rows;
+ * *tx, *ty (may be NULL) receive the grid; 0 when W, H, tw or th is 0.
+ *
+ * qb3x_encode_mosaic: tile k = j * tx + i is the tile at (i * tw, j * th).  Its container goes to d_dst + k * dst_pitch, its
+ * index to d_index + k * qb3x_index_size(p) (or d_index is NULL), its size to sizes[k]; returns the number of tiles encoded.
+ * Pixel (x, y) of tile k is raster pixel (min(i * tw + x, W - 1), min(j * th + y, H - 1)): tiles that cross the right or
+ * bottom edge repeat the raster's last column and row.  The bytes of container k are, for every mode and handle setting,
+ * what qb3x_encode_tiles writes for that tile given as a contiguous image -- the raw-stored fallback of an incompressible
+ * tile, the restart tables under qb3x_set_encoder_index_chunk and the band state left in the handle (the last tile's)
+ * included.  Tiles inside the raster are read in place; the edge tiles (at most tx + ty - 1) are built in memory of the
+ * handle's by one launch.  Refused with QB3E_EINV (qb3_get_encoder_state), 0 returned, nothing launched or written:
+ * whatever qb3x_encode_tiles refuses, W == 0 or H == 0, a nonzero stride below W * bands, d_raster == NULL.
+ *
+ * qb3x_decode_mosaic: containers as for qb3x_decode_tiles, tile k at d_src + k * src_pitch, p parsed from tile 0.  Tile k's
+ * pixels go to the raster at (i * tw, j * th), clipped to W x H: no byte outside the H runs of W * bands values is written
+ * -- not the gaps of a wide stride, nothing behind the last row.  qb3x_decode_tile_ok(p, k) as after qb3x_decode_tiles; a
+ * tile that fails leaves its own rectangle unspecified and nothing else.  Tiles of another kind than tile 0, quanta, compat
+ * flags, d_index and tables inside the containers: as qb3x_decode_tiles.  Returns the number of tiles decoded; 0 for what
+ * qb3x_decode_tiles refuses and for the raster arguments qb3x_encode_mosaic refuses. */
+size_t qb3x_mosaic_tiles(size_t W, size_t H, size_t tw, size_t th, size_t *tx, size_t *ty);
+size_t qb3x_encode_mosaic(encsp p, const void *d_raster, size_t W, size_t H, size_t raster_stride,
+                          void *d_dst, size_t dst_pitch, void *d_index, size_t *sizes, void *stream);
+size_t qb3x_decode_mosaic(decsp p, const void *d_src, size_t src_pitch, const size_t *sizes,
+                          size_t W, size_t H, void *d_raster, size_t raster_stride,
+                          const void *d_index, void *stream);
+
 /* qb3_read_start for the device flavour: `header` is a host copy of the FIRST header_size bytes of a container of
  * stream_size bytes (the parser never reads beyond the copy; qb3_read_info fails when the copy ends before the
  * container's "DT" mark).  qb3x_header_size_bound(first bytes, how many) says how many bytes always suffice,

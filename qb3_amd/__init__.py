@@ -96,6 +96,9 @@ _PROTOS = {
     "qb3x_encode_tiles": (_sz, [_vp, _vp, _sz, _sz, _vp, _sz, _vp, C.POINTER(_sz), _vp]),
     "qb3x_decode_tiles": (_sz, [_vp, _vp, _sz, _sz, C.POINTER(_sz), _vp, _sz, _vp, _vp]),
     "qb3x_decode_tile_ok": (C.c_int, [_vp, _sz]),
+    "qb3x_mosaic_tiles": (_sz, [_sz, _sz, _sz, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
+    "qb3x_encode_mosaic": (_sz, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp, C.POINTER(_sz), _vp]),
+    "qb3x_decode_mosaic": (_sz, [_vp, _vp, _sz, C.POINTER(_sz), _sz, _sz, _vp, _sz, _vp, _vp]),
     "qb3x_decode_window_device": (_sz, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp]),
     "qb3x_read_window": (_sz, [_vp, _sz, _sz, _sz, _sz, _vp, _sz]),
     "qb3x_window_segments": (_sz, [_vp, _sz, _sz, _sz, _sz, C.POINTER(_sz)]),

@@ -160,7 +160,8 @@ int launch_decode(const Geometry &g, const DecPlan &plan_in, const uint32_t *in3
     const uint64_t bits = tb.n ? tb.max_bits : in_bits;     // the (longest) stream
     const TableShape table = table_shape(g, ix);
     const bool walk_memory_ok = walk_tab && walk_tab_bytes >= walk_table_min_bytes(a.ntiles, g.tsz) && !tuning().slow_walk;
-    const DecKernel picked = pick_dec_kernel(g, plan_in, img, tb.dst_pitch);
+    const TileGridRule tg = make_tile_grid(tb);      // (a decoder's "dst" is the image)
+    const DecKernel picked = pick_dec_kernel(g, plan_in, img, tile_pitch_bits(tg, true));
     const DecFront front = pick_dec_front(g, plan_in, picked, index != nullptr, table, walk_memory_ok, dec_index_walk_best_ok(a));
     const DecKernel k = front == DecFront::pieces ? DecKernel::generic : picked;
     // the staging of the kernels that have one: a third above the average for 16-bit data (worst case 278 bits a unit), half for
@@ -187,14 +188,16 @@ int launch_decode(const Geometry &g, const DecPlan &plan_in, const uint32_t *in3
         cap = (cap + cap / 2 + 64 + 3) & ~(uint64_t)3;
         if (bits && cap <= 24 * 1024 / 4) a.seg_cap_dw = (uint32_t)cap;
     }
-    a.in32 = in32; a.in_bit0 = in_bit0; a.in_bits = in_bits; a.img = img; a.ts_in = tb.src_pitch; a.ts_img = tb.dst_pitch; a.tile_bits = tile_bits;
+    a.in32 = in32; a.in_bit0 = in_bit0; a.in_bits = in_bits; a.img = img; a.ts_in = tg.src; a.ts_img = tg.dst; a.tile_bits = tile_bits;
+    a.tcols = tg.cols; a.tmagic = tg.magic; a.tr_in = tg.src_row; a.tr_img = tg.dst_row;
     uint8_t *w = (uint8_t *)ws;
     const bool rebuild = index == nullptr;
     // workspace: [status words, 64 bytes per 16 tiles][rebuilt indices, one per tile]
     const size_t status_bytes = ((4 * (size_t)a.ntiles + 63) / 64) * 64;
     *status_out = a.status = (uint32_t *)w;
     a.idx = index_view(g, rebuild ? (void *)(w + status_bytes) : const_cast<void *>(index));
-    a.ts_idx = rebuild ? align8(index_bytes(g)) : tb.idx_pitch;
+    a.ts_idx = rebuild ? align8(index_bytes(g)) : tg.idx;
+    a.tr_idx = rebuild ? a.tcols * a.ts_idx : tg.idx_row;         // (the rebuilt indices stand in the workspace, one a launch tile)
     // a strip is one launch of a wave-per-segment decoder; where one applies but the memory is not aligned for it the generic kernel was
     // picked, which does not decode ranges of segments: refused before anything is enqueued.  (The host's strips go to pool memory.)
     if (strip && picked == DecKernel::generic && aligned_dec_kernel(g, plan_in) != DecKernel::generic) {
@@ -208,7 +211,7 @@ int launch_decode(const Geometry &g, const DecPlan &plan_in, const uint32_t *in3
     a.bpp = plan.bpp; a.passes = plan.passes; a.in_cap_dw = (plan.px || plan.px16 || plan.px_best || plan.pxw || plan.pxw_best || plan.pxu || plan.pxu_best) ? plan.px_cap_dw : plan.in_cap_dw;
     a.px_ng = plan.px16 ? plan.px16_ng : 1; a.px_magic_ng = magic_div(a.px_ng);
     a.wide_band = tuning().wide_band ? (uint32_t)tuning().wide_band : wide_band;
-    a.px_aligned = !(g.w & 3) && !((g.stride * g.tsz) & 3) && !((uintptr_t)img & 3) && !(tb.dst_pitch & 3);
+    a.px_aligned = !(g.w & 3) && !((g.stride * g.tsz) & 3) && !((uintptr_t)img & 3) && !(tile_pitch_bits(tg, true) & 3);
     a.magic_bpp = magic_div(plan.bpp); a.magic_dpr = magic_div(a.dpr); a.magic_bands = magic_div(g.bands);
     if (g.tsz != 1 && g.tsz != 2 && g.tsz != 4 && g.tsz != 8) { set_error("decode: bad value size", 0); return -1; }
     return launch_decode_all(a, plan, k, front, table, st, walk_tab, walk_tab_bytes, walk_memory_ok, bits, strip);

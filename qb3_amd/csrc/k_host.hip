@@ -208,6 +208,16 @@ IndexView index_view(const Geometry &g, void *base) {
 
 uint32_t magic_div(uint32_t d) { return d == 1 ? 0u : (uint32_t)(((1ull << 32) + d - 1) / d); }   // exact for n*d < 2^32/d-ish, n small
 
+// t / cols for every launch tile t < 65536 by one multiply (exact: t * (magic * cols - 2^32) < 2^32 for cols < 65536)
+TileGridRule make_tile_grid(const TileBatch &tb) {
+    TileGridRule r = { 0, 0, tb.src_pitch, 0, tb.dst_pitch, 0, tb.idx_pitch, 0 };
+    if (!tb.cols || tb.cols >= tb.n) return r;                  // one row
+    if (tb.cols == 1) { r.src = tb.src_row; r.dst = tb.dst_row; r.idx = tb.idx_row; return r; }     // one column
+    r.cols = tb.cols; r.magic = magic_div(tb.cols);
+    r.src_row = tb.src_row; r.dst_row = tb.dst_row; r.idx_row = tb.idx_row;
+    return r;
+}
+
 uint32_t max_unit_bits(uint32_t tsz, uint32_t mode) {
     const uint32_t ub = tsz == 1 ? 3 : tsz == 2 ? 4 : tsz == 4 ? 5 : 6;
     const uint32_t plain = ub + 2 + 16 * (8 * tsz + 1);
@@ -340,7 +350,7 @@ static void launch_enc_units(const EncArgs &a, const EncPlan &plan, hipStream_t 
         launch_enc_px(a, plan, st);
     }
     else if (plan.px16 && a.g.tsz == 2 && ((uintptr_t)a.img & 1) == 0) { ProfScope ps("enc_units", st); launch_enc_px16(a, plan, st); }
-    else if (plan.pxw && ((uintptr_t)a.img & (a.g.tsz - 1)) == 0 && !(a.ts_img & (a.g.tsz - 1))) { ProfScope ps("enc_units", st); launch_enc_pxw(a, plan, st); }
+    else if (plan.pxw && ((uintptr_t)a.img & (a.g.tsz - 1)) == 0 && !((a.ts_img | a.tr_img) & (a.g.tsz - 1))) { ProfScope ps("enc_units", st); launch_enc_pxw(a, plan, st); }
     else { ProfScope ps("enc_units", st); launch_enc_generic(a, plan, st); }
 }
 static int launch_encode_all(const EncArgs &a, const EncPlan &plan, hipStream_t st) {
@@ -357,7 +367,9 @@ static bool make_enc_args(EncArgs &a, const Geometry &g, const EncPlan &plan, co
     a.zrun_probe = zrun_probe ? 1u : 0u;
     a.ix_dst = ix.base; a.ix_K = ix.K; a.ix_E = ix.entry_bytes; a.ix_per_chunk = ix.per_chunk; a.ix_blocks = ix.blocks;
     a.ix_spe = g.seg_blocks ? ix.blocks / g.seg_blocks : 0;
-    a.ntiles = tb.n ? tb.n : 1; a.ts_img = tb.src_pitch; a.ts_out = tb.dst_pitch; a.ts_ws = tb.ws_pitch; a.ts_idx = tb.idx_pitch;
+    const TileGridRule tg = make_tile_grid(tb);
+    a.ntiles = tb.n ? tb.n : 1; a.ts_img = tg.src; a.ts_out = tg.dst; a.ts_ws = tb.ws_pitch; a.ts_idx = tg.idx;
+    a.tcols = tg.cols; a.tmagic = tg.magic; a.tr_img = tg.src_row; a.tr_out = tg.dst_row; a.tr_idx = tg.idx_row;
     a.hdr_len = hdr_len <= sizeof(a.hdr) ? hdr_len : 0;
     a.hdr_back = a.hdr_len + (ix.base ? (uint32_t)ix_total_bytes(ix) + 2 : 0);
     for (uint32_t i = 0; i < a.hdr_len; i++) a.hdr[i] = hdr[i];
@@ -377,7 +389,7 @@ static bool make_enc_args(EncArgs &a, const Geometry &g, const EncPlan &plan, co
     a.slot_dw = L.slot_dw;
     a.px_ng = plan.px16 ? plan.px16_ng : 1; a.px_magic_ng = magic_div(a.px_ng);
     a.px16_bg = g.tsz == 2 ? px16_bands_per_lane(g) : 0;
-    a.px_aligned = !(g.w & 3) && !((g.stride * g.tsz) & 3) && !((uintptr_t)img & 3) && !(tb.src_pitch & 3);
+    a.px_aligned = !(g.w & 3) && !((g.stride * g.tsz) & 3) && !((uintptr_t)img & 3) && !(tile_pitch_bits(tg, false) & 3);
     a.res = (EncResult *)(w + L.res);
     a.st = st_in;
     a.ix_bl = ix.base && ix.block_lens;

@@ -67,7 +67,7 @@ QB3_API void qb3_reset_encoder(encsp p) {
 
 QB3_API void qb3_destroy_encoder(encsp p) {
     if (!p) return;
-    release_all({&p->d_img, &p->d_out, &p->d_ws, &p->d_q, &p->d_idx, &p->d_rle});
+    release_all({&p->d_img, &p->d_out, &p->d_ws, &p->d_q, &p->d_idx, &p->d_rle, &p->d_mos});
     p->stager.release(); p->stager2.release(); p->pipe.release();
     delete p;
 }
@@ -504,7 +504,7 @@ QB3_API size_t qb3x_index_size(const encsp p) {
 // ---------------------------------------------------------------- decoder handle
 QB3_API void qb3_destroy_decoder(decsp p) {
     if (!p) return;
-    release_all({&p->d_in, &p->d_img, &p->d_ws, &p->d_ix, &p->d_rle, &p->d_tab, &p->d_win, &p->d_wst, &p->d_wout, &p->d_wsrc, &p->d_wdesc, &p->d_rg, &p->d_wfull, &p->d_wgat});
+    release_all({&p->d_in, &p->d_img, &p->d_ws, &p->d_ix, &p->d_rle, &p->d_tab, &p->d_win, &p->d_wst, &p->d_wout, &p->d_wsrc, &p->d_wdesc, &p->d_rg, &p->d_wfull, &p->d_wgat, &p->d_mos});
     p->h_wdesc.release(); p->h_wst.release(); p->h_rg.release(); p->h_wgat.release();
     p->stager.release(); p->stager2.release(); p->pipe.release();
     delete p;

@@ -174,7 +174,16 @@ inline size_t ix_total_bytes(const IxTable &t) { return ix_chunks(t) * (IX_HEAD 
 
 // Batched tiles: n images/streams laid out at fixed byte pitches, processed by one set of launches (blockIdx.y).
 // n == 0 means a single image.  ws_pitch = plan.ws_bytes of one tile; idx_pitch = index_bytes of one tile.
-struct TileBatch { uint32_t n = 0; uint64_t src_pitch = 0, dst_pitch = 0, ws_pitch = 0, idx_pitch = 0; uint64_t max_bits = 0; /* decode: the longest stream */ };
+struct TileBatch { uint32_t n = 0; uint64_t src_pitch = 0, dst_pitch = 0, ws_pitch = 0, idx_pitch = 0; uint64_t max_bits = 0; /* decode: the longest stream */
+    // A tile GRID (the tiles of a mosaic where they lie in the raster): cols > 0 makes launch tile t tile (t / cols, t % cols); images, containers
+    // and the caller's index then go *_row bytes from row to row and *_pitch bytes from column to column (n is a multiple of cols).  The
+    // workspace, the stream lengths and the status words stay indexed by t.  cols == 0: one row of n tiles, the *_row fields are not read.
+    uint32_t cols = 0; uint64_t src_row = 0, dst_row = 0, idx_row = 0; };
+// what the kernels divide by (EncArgs / DecArgs::tcols, tmagic, the three pitch pairs): one row of tiles takes no division at all (magic 0),
+// a column of tiles is a row whose column pitch is the row pitch
+struct TileGridRule { uint32_t cols, magic; uint64_t src, src_row, dst, dst_row, idx, idx_row; };
+TileGridRule make_tile_grid(const TileBatch &tb);
+inline uint64_t tile_pitch_bits(const TileGridRule &r, bool dst) { return dst ? (r.dst | r.dst_row) : (r.src | r.src_row); }     // low bits set: some tile is off that alignment
 // Plain 8- and 16-bit streams (no index, no restart table) are walked through a table of unit lengths by position (k_dec_walk.hip).
 // walk_table_bytes: memory that takes the whole call in one round; less means more rounds, down to walk_table_min_bytes.
 size_t walk_table_bytes(uint32_t ntiles, uint64_t max_bits, uint32_t tsz);
@@ -364,6 +373,15 @@ constexpr size_t WIN_PIECE_BYTES = 32;
 int launch_decode_windows_ranged(const WinKernels &k, const Geometry &g, const DecPlan &plan, uint32_t in_bit0, uint64_t in_bits, const void *h_descs,
                                  const void *d_descs, size_t n, const void *d_pieces, size_t npieces, const void *d_entries, const uint32_t *d_words,
                                  uint32_t *d_status, void *stream, const IxTable &ix);
+
+// Mosaics (k_mosaic.hip): the tiles that cross a raster's right or bottom edge are coded from, and decoded into, memory of the handle's.
+// One descriptor a tile and ONE launch for n of them copies the rows of a rectangle and, where the destination is larger, repeats the
+// rectangle's last pixel to the right and its last row downwards: src to dst, spitch / dpitch bytes between rows, cw bytes of ch rows
+// copied, ow >= cw bytes of oh >= ch rows written.  pad (raster -> tile): ow x oh is the tile; crop (tile -> raster): ow == cw, oh == ch.
+// No byte outside the ow x oh destination is written, none outside the cw x ch source is read.
+struct MosaicRect { const void *src; uint64_t spitch; void *dst; uint64_t dpitch; uint32_t cw, ch, ow, oh; };
+constexpr size_t MOSAIC_RECT_BYTES = 48;
+int launch_mosaic_rects(const void *d_descs, size_t n, uint32_t max_rows, uint32_t pixel_bytes, bool pad, void *stream);
 
 // Reindex (k_reindex.hip): the table chunks this library's encoder writes for a raster, made from the index a plain walk of its stream
 // has rebuilt (launch_decode with index == nullptr leaves it in ws behind the status words), and the new container around them.

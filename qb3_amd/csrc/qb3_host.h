@@ -86,6 +86,7 @@ struct encs {
     bool away;
     int ix_chunk;           // qb3x_set_encoder_index_chunk: embed the restart table ("ix" chunks); 2: with block lengths
     DevBuf d_img, d_out, d_ws, d_q, d_idx, d_rle;      // d_rle: workspace of the RLE0 passes (k_rle0.hip)
+    DevBuf d_mos;                                      // qb3x_encode_mosaic: the edge tiles' descriptors and their replicated images
     Stager stager, stager2;                            // (stager2: the download ring of a pipelined host call)
     Pipe pipe;                                         // ... its streams and events
 };
@@ -126,6 +127,7 @@ struct decs {
     DevBuf d_wfull, d_wgat;                            // band-selected windows (api_window_bands.cpp): full-band windows a window kernel wrote for the gather; the gather's descriptors
     PinBuf h_wgat;                                     // ... their pinned host copy
     size_t win_gathers = 0;                            // ... gather launches of the last band-selected call (qb3x_last_window_gathers)
+    DevBuf d_mos;                                      // qb3x_decode_mosaic: the edge tiles' descriptors and the whole tiles they decode to
     Stager stager, stager2;                            // (stager2: the download ring of a pipelined host call)
     Pipe pipe;                                         // ... its streams and events
     // a ranged handle (qb3x_open_ranged, api_ranged.cpp): the caller's reader, the container's size, what the last call asked of the reader
@@ -168,6 +170,21 @@ size_t write_headers(const encs *p, uint8_t *dst, bool with_dt = true);
 decsp read_start_impl(void *source, size_t hdr_avail, size_t source_size, size_t *image_size);
 qb3dev::IxTable handle_table(const decs *p, const uint8_t *base);
 qb3dev::Geometry decoder_geometry(const decs *p, size_t w, size_t h, size_t stride);
+
+// api_tiles.cpp: equally shaped tiles of one call that go through one set of launches.  Tile u is tile (u / cols, u % cols) of a grid:
+// its image img_row bytes down and img_col bytes along from `img`, its container (size, index, outcome) number k0 + (u / cols) * k_row +
+// u % cols of the call's.  n is a multiple of cols; tiles back to back are one row (cols == n).  The mosaic calls (api_mosaic.cpp) hand
+// in up to three grids: the tiles inside the raster where they lie, the bottom row and the right column in memory of the handle's.
+struct TileGrid {
+    size_t n, cols;
+    const void *img;            // encode: the source; decode: the destination
+    size_t img_col, img_row;
+    size_t stride;              // values between the pixel rows of a tile (0: tight); the handle's own setting is set aside for the call
+    size_t k0, k_row;
+};
+size_t encode_tile_grids(encsp p, const TileGrid *grids, size_t ngrids, void *d_dst, size_t dst_pitch, void *d_index, size_t *sizes, void *stream);
+size_t decode_tile_grids(decsp p, const void *d_src, size_t n, size_t src_pitch, const size_t *sizes, const TileGrid *grids, size_t ngrids,
+                         const void *d_index, void *stream);
 
 // what the window calls say once (api_window.cpp, api_ranged.cpp): values between the destination's rows; is the rectangle inside the raster
 inline size_t win_stride(const decs *p, const qb3x_window &w) { return w.dst_stride ? w.dst_stride : w.w * p->nbands; }

@@ -207,6 +207,11 @@ struct EncArgs {
     uint32_t *recode_need, *recode_list, *recode_n;    //   ... chunks to code again: flag per chunk, list, count
     uint32_t ntiles;
     uint64_t ts_img, ts_out, ts_ws, ts_idx;     // batched tiles: byte strides from tile to tile (blockIdx.y = tile)
+    // ... of a tile GRID (a mosaic's tiles where they lie in the raster, TileBatch::cols): launch tile t is tile (t / tcols, t % tcols); the image,
+    // the container and the caller's index go tr_* bytes from row to row and ts_* from column to column, the workspace t * ts_ws.
+    // A plain batch is one row: tmagic == 0 (t / tcols by fastdiv's rule; make_tile_grid, k_host.hip)
+    uint32_t tcols, tmagic;
+    uint64_t tr_img, tr_out, tr_idx;
     uint32_t hdr_len;       // container header bytes to put in front of the stream (enc_finish_kernel)
     uint32_t hdr_back;      // distance from the container start to the stream start (= hdr_len without an index chunk)
     uint8_t hdr[80];        // at most 11 + 20 (CB) + 12 (QV) + 12 (SC) + 12 (ix head) bytes
@@ -235,15 +240,17 @@ struct EncArgs {
 template <typename P> __device__ __forceinline__ P *shift_ptr(P *p, uint64_t bytes) { return p ? (P *)((uint8_t *)p + bytes) : p; }
 __device__ __forceinline__ EncArgs enc_for_tile(EncArgs a, uint32_t t) {
     if (t) {
-        a.img = (const uint8_t *)a.img + t * a.ts_img;
-        a.out32 = shift_ptr(a.out32, t * a.ts_out);
-        const uint64_t w = t * a.ts_ws, x = t * a.ts_idx;
+        const uint32_t r = __umulhi(t, a.tmagic), c = t - r * a.tcols;
+        a.img = (const uint8_t *)a.img + (r * a.tr_img + c * a.ts_img);
+        const uint64_t o = r * a.tr_out + c * a.ts_out;
+        a.out32 = shift_ptr(a.out32, o);
+        const uint64_t w = t * a.ts_ws, x = r * a.tr_idx + c * a.ts_idx;
         a.chunk_bits = shift_ptr(a.chunk_bits, w); a.chunk_off = shift_ptr(a.chunk_off, w); a.group_sum = shift_ptr(a.group_sum, w);
         a.scratch = shift_ptr(a.scratch, w); a.seams = shift_ptr(a.seams, w); a.res = shift_ptr(a.res, w);
         a.cw_has = shift_ptr(a.cw_has, w); a.cw_val = shift_ptr(a.cw_val, w); a.centry = shift_ptr(a.centry, w); a.cw_used = shift_ptr(a.cw_used, w); a.seg_from_entry = shift_ptr(a.seg_from_entry, w); a.recode_need = shift_ptr(a.recode_need, w); a.recode_list = shift_ptr(a.recode_list, w); a.recode_n = shift_ptr(a.recode_n, w); a.centry_parts = shift_ptr(a.centry_parts, w);
         a.idx.bitpos = shift_ptr(a.idx.bitpos, x); a.idx.prev = shift_ptr(a.idx.prev, x); a.idx.cf = shift_ptr(a.idx.cf, x);
         a.idx.rung = shift_ptr(a.idx.rung, x); a.idx.ulen = shift_ptr(a.idx.ulen, x);
-        a.ix_dst = shift_ptr(a.ix_dst, t * a.ts_out);     // (the restart table sits at the same place in every tile's container)
+        a.ix_dst = shift_ptr(a.ix_dst, o);                // (the restart table sits at the same place in every tile's container)
     }
     return a;
 }
@@ -340,7 +347,9 @@ struct DecArgs {
     // batched tiles (blockIdx.y = tile): byte strides, and each tile's stream length in bits (null: in_bits for all)
     uint32_t ntiles;
     uint64_t ts_in, ts_img, ts_idx;
-    const uint64_t *tile_bits;
+    const uint64_t *tile_bits;      // (indexed by launch tile, like the status words)
+    uint32_t tcols, tmagic;         // a tile grid, as EncArgs has it: rows of tcols tiles, tr_* bytes from row to row
+    uint64_t tr_in, tr_img, tr_idx;
     // band-selected windows (the SEL instantiations of the lane-per-unit window kernels, qb3_win_unit.h; nobody else reads them):
     // the band of output slot k in nibble k, the slots of a pixel (1..16), and x / nsel as fastdiv takes it
     uint64_t sel_nibs;
@@ -417,12 +426,14 @@ __device__ __forceinline__ const uint8_t *ix_entry_at(const uint8_t *base, uint3
 __device__ __forceinline__ DecArgs dec_for_tile(DecArgs a, uint32_t t) {
     if (a.tile_bits) a.in_bits = a.tile_bits[t];
     if (t) {
-        a.in32 = shift_ptr(a.in32, t * a.ts_in);
-        a.img = shift_ptr((uint8_t *)a.img, t * a.ts_img);
-        const uint64_t x = t * a.ts_idx;
+        const uint32_t r = __umulhi(t, a.tmagic), c = t - r * a.tcols;
+        const uint64_t i = r * a.tr_in + c * a.ts_in;
+        a.in32 = shift_ptr(a.in32, i);
+        a.img = shift_ptr((uint8_t *)a.img, r * a.tr_img + c * a.ts_img);
+        const uint64_t x = r * a.tr_idx + c * a.ts_idx;
         a.idx.bitpos = shift_ptr(a.idx.bitpos, x); a.idx.prev = shift_ptr(a.idx.prev, x); a.idx.cf = shift_ptr(a.idx.cf, x);
         a.idx.rung = shift_ptr(a.idx.rung, x); a.idx.ulen = shift_ptr(a.idx.ulen, x);
-        a.ix = shift_ptr(a.ix, t * a.ts_in);               // (the restart table sits at the same place in every tile's container)
+        a.ix = shift_ptr(a.ix, i);                         // (the restart table sits at the same place in every tile's container)
         a.status += t;
     }
     return a;

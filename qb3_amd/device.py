@@ -261,6 +261,88 @@ class TileBatchCoder:
         return out
 
 
+class MosaicCoder:
+    """qb3x_encode_mosaic / qb3x_decode_mosaic on torch tensors: a W x H raster on the device as a grid of independently coded
+    tiles of tw x th pixels, coded from and decoded to the raster where it lies.  Tile k = j * tx + i has its container at
+    k * pitch of `dst`, its size in `sizes`, its out-of-band index at k * index_bytes of `index`."""
+
+    def __init__(self, W, H, bands, dtype, tile=(512, 512), mode=QB3M_FTL, index_chunk=False, want_index=False, device="cuda"):
+        self.W, self.H, self.bands, self.dtype, self.mode = W, H, bands, dtype, mode
+        self.tw, self.th = tile
+        tx, ty = _sz(), _sz()
+        self.n = lib.qb3x_mosaic_tiles(W, H, self.tw, self.th, C.byref(tx), C.byref(ty))
+        self.tx, self.ty = tx.value, ty.value
+        self.p = lib.qb3_create_encoder(self.tw, self.th, bands, dtype) if self.n else None
+        if not self.p:
+            raise ValueError("qb3_create_encoder refused the tile geometry")
+        lib.qb3_set_encoder_mode(self.p, mode)
+        lib.qb3x_set_encoder_index_chunk(self.p, int(index_chunk))
+        self.pitch = (lib.qb3_max_encoded_size(self.p) + 3) // 4 * 4
+        self.index_bytes = lib.qb3x_index_size(self.p) if want_index else 0
+        self.dst = torch.empty(self.n * self.pitch, dtype=torch.uint8, device=device)
+        self.index = torch.empty(max(1, self.n * self.index_bytes), dtype=torch.uint8, device=device) if want_index else None
+        self.sizes = (_sz * self.n)()
+        self.d = None
+
+    def close(self):
+        if lib is None:
+            return
+        if self.p:
+            lib.qb3_destroy_encoder(self.p)
+            self.p = None
+        if self.d:
+            lib.qb3_destroy_decoder(self.d)
+            self.d = None
+
+    __del__ = close
+
+    def _raster(self, t):
+        """(pointer, stride in values) of a raster tensor: contiguous, or a 2-D / 3-D view whose rows are contiguous"""
+        assert t.is_cuda and TYPESIZE[self.dtype] == t.element_size()
+        if t.is_contiguous():
+            assert t.numel() >= self.W * self.H * self.bands
+            return t.data_ptr(), 0
+        rowvals = self.W * self.bands
+        v = t.reshape(self.H, rowvals) if t.dim() == 3 and t.stride(1) == self.bands and t.stride(2) == 1 else t
+        assert v.dim() == 2 and tuple(v.shape) == (self.H, rowvals) and v.stride(1) == 1 and v.stride(0) >= rowvals, \
+            "a strided raster is a (H, W * bands) view with contiguous rows"
+        return v.data_ptr(), v.stride(0)
+
+    def encode(self, raster):
+        """raster: device tensor of the raster's type, contiguous or a strided 2-D view (H, W * bands).  Returns the tile sizes."""
+        ptr, stride = self._raster(raster)
+        lib.qb3_reset_encoder(self.p)
+        lib.qb3_set_encoder_mode(self.p, self.mode)
+        k = lib.qb3x_encode_mosaic(self.p, _vp(ptr), self.W, self.H, stride, _vp(self.dst.data_ptr()), self.pitch,
+                                   _vp(self.index.data_ptr()) if self.index is not None else None, self.sizes, _stream_ptr())
+        if k != self.n:
+            raise RuntimeError(f"qb3x_encode_mosaic coded {k} of {self.n} tiles (state {lib.qb3_get_encoder_state(self.p)}): {last_error()}")
+        if self.d:                      # the containers changed: parse tile 0 again at the next decode
+            lib.qb3_destroy_decoder(self.d)
+            self.d = None
+        return list(self.sizes)
+
+    def container(self, k):
+        """tile k's container: a view of the buffer the object owns"""
+        return self.dst[k * self.pitch:k * self.pitch + self.sizes[k]]
+
+    def decode(self, out, use_index=True, compat=None):
+        """decodes the containers made by encode() into the raster tensor `out` (as encode takes it)."""
+        ptr, stride = self._raster(out)
+        if self.d is None:
+            dims = (_sz * 3)()
+            self.d = lib.qb3x_read_start_device(_vp(self.dst.data_ptr()), int(self.sizes[0]), dims, _stream_ptr())
+            if not self.d:
+                raise ValueError("tile 0 does not parse")
+        if compat is not None:
+            lib.qb3x_set_decoder_compat(self.d, int(compat))
+        k = lib.qb3x_decode_mosaic(self.d, _vp(self.dst.data_ptr()), self.pitch, self.sizes, self.W, self.H, _vp(ptr), stride,
+                                   _vp(self.index.data_ptr()) if (use_index and self.index is not None) else None, _stream_ptr())
+        if k != self.n:
+            raise RuntimeError(f"qb3x_decode_mosaic decoded {k} of {self.n} tiles: {last_error()}")
+        return out
+
+
 def profile_enable(on=True):
     """True / 1: every kernel; 2: skip the microsecond kernels (less event traffic in a timed loop); 3: the coding kernels (`*_units`) alone; False / 0: off."""
     lib.qb3x_profile_enable(int(on))

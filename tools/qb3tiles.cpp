@@ -1,9 +1,10 @@
-// tools/qb3tiles.cpp -- tile batcher over qb3x_encode_tiles / qb3x_decode_tiles (include/qb3x.h): the caller the
+// tools/qb3tiles.cpp -- tile batcher over qb3x_encode_mosaic / qb3x_decode_mosaic (include/qb3x.h): the caller the
 // reference does not ship but its users write.  GDAL's MRF driver keeps a raster as a grid of independently coded QB3
 // tiles, one qb3_encode call per tile (reference README.md:30-31; the reference's own nearest pattern is cqb3's folder
 // mode, cqb3.cpp:614-641: one file, one call).  Here a whole raster is cut into tiles, every tile is an independent
-// QB3 container -- exactly what qb3_encode would write for it -- and all tiles of a call go through ONE set of kernel
-// launches.
+// QB3 container -- exactly what qb3_encode would write for it.  The raster goes to the device once, as it is: the library
+// codes the tiles where they lie in it (and decodes them back into place), a set of kernel launches for the tiles inside
+// the raster and one for those on its right and bottom edge.
 //
 //   qb3tiles -e [-v] [-b|-f] [-t N] input.pnm out.qts          cut into N x N tiles (default 512), code, store
 //   qb3tiles -d [-v] in.qts output.pnm                          decode every tile, reassemble the raster
@@ -11,7 +12,8 @@
 //
 // Tile-set file (.qts): "QTS1", u32 raster width, height, bands, dtype, tile edge, tiles per row, tiles per column, then
 // one (u64 offset, u64 size) pair per tile in row-major order, then the containers back to back.  Edge tiles are padded
-// by repeating the raster's last column / row (every tile of a call has one geometry) and cropped on decode.
+// by repeating the raster's last column / row (every tile of a call has one geometry) and cropped on decode: both by the
+// library, on the device.
 // Input is binary PNM (P5 / P6, 8 or 16 bit) like tools/cqb3x.cpp.
 #include "QB3.h"
 #include "qb3x.h"
@@ -103,36 +105,24 @@ int encode(const std::string &in, const std::string &out, size_t T, int mode, bo
     Raster r;
     if (!read_pnm(in, r)) return fail("cannot read " + in + " as binary PNM");
     if (T < 4 || T > 65536) return fail("tile edge out of range");
-    const size_t tsz = r.type == QB3_U8 ? 1 : 2, pix = r.bands * tsz;
-    const size_t tx = (r.w + T - 1) / T, ty = (r.h + T - 1) / T, n = tx * ty, raw = T * T * pix;
-    // cut: tile (i, j) at tile index j * tx + i, padded by edge replication
-    std::vector<uint8_t> tiles(n * raw);
-    for (size_t j = 0; j < ty; j++)
-        for (size_t i = 0; i < tx; i++) {
-            uint8_t *t = tiles.data() + (j * tx + i) * raw;
-            for (size_t y = 0; y < T; y++) {
-                const size_t sy = std::min(j * T + y, r.h - 1);
-                const uint8_t *row = r.px.data() + sy * r.w * pix;
-                const size_t x0 = i * T, nx = x0 + T <= r.w ? T : r.w - x0;
-                memcpy(t + y * T * pix, row + x0 * pix, nx * pix);
-                for (size_t x = nx; x < T; x++) memcpy(t + (y * T + x) * pix, row + (r.w - 1) * pix, pix);
-            }
-        }
+    size_t tx = 0, ty = 0;
+    const size_t n = qb3x_mosaic_tiles(r.w, r.h, T, T, &tx, &ty);       // tile (i, j) is tile j * tx + i
+    if (!n) return fail("empty raster");
     encsp p = qb3_create_encoder(T, T, r.bands, (qb3_dtype)r.type);
     if (!p) return fail("qb3_create_encoder refused the tile geometry");
     qb3_set_encoder_mode(p, (qb3_mode)mode);
     if (tables) qb3x_set_encoder_index_chunk(p, tables);  // every tile carries its restart table (2: with block lengths): the set decodes in parallel inside every tile
     const size_t pitch = (qb3_max_encoded_size(p) + 3) / 4 * 4;
-    DevMem d_src(n * raw), d_dst(n * pitch);
+    DevMem d_src(r.px.size()), d_dst(n * pitch);
     if (!d_src.p || !d_dst.p) { qb3_destroy_encoder(p); return fail("out of device memory"); }
     std::vector<size_t> sizes(n);
     const double t0 = now();
-    if (hipMemcpy(d_src.p, tiles.data(), tiles.size(), hipMemcpyHostToDevice) != hipSuccess) { qb3_destroy_encoder(p); return fail("upload failed"); }
+    if (hipMemcpy(d_src.p, r.px.data(), r.px.size(), hipMemcpyHostToDevice) != hipSuccess) { qb3_destroy_encoder(p); return fail("upload failed"); }
     const double t1 = now();
-    const size_t done = qb3x_encode_tiles(p, d_src.p, n, raw, d_dst.p, pitch, nullptr, sizes.data(), nullptr);
+    const size_t done = qb3x_encode_mosaic(p, d_src.p, r.w, r.h, 0, d_dst.p, pitch, nullptr, sizes.data(), nullptr);
     const double t2 = now();
     qb3_destroy_encoder(p);
-    if (done != n) return fail(std::string("qb3x_encode_tiles: ") + qb3x_last_error());
+    if (done != n) return fail(std::string("qb3x_encode_mosaic: ") + qb3x_last_error());
     // gather the containers: header, table, data
     QtsHeader h;
     memcpy(h.sig, "QTS1", 4);
@@ -168,13 +158,17 @@ int decode(const std::string &in, const std::string &out, bool verbose) {
     QtsHeader h;
     std::vector<QtsEntry> tab;
     if (!read_file(in, f) || !parse_qts(f, h, tab)) return fail(in + " is not a tile set");
-    const size_t n = tab.size(), T = h.tile, tsz = (h.dtype < 2) ? 1 : (h.dtype < 4) ? 2 : (h.dtype < 6) ? 4 : 8, pix = h.bands * tsz, raw = T * T * pix;
+    const size_t n = tab.size(), T = h.tile, tsz = (h.dtype < 2) ? 1 : (h.dtype < 4) ? 2 : (h.dtype < 6) ? 4 : 8, pix = h.bands * tsz;
+    if (!h.w || !h.h || qb3x_mosaic_tiles(h.w, h.h, T, T, nullptr, nullptr) != n || (h.w + T - 1) / T != h.tx) return fail(in + ": the tile grid does not fit the raster");
+    Raster r;
+    r.w = h.w; r.h = h.h; r.bands = h.bands; r.type = (int)h.dtype;
+    r.px.resize(r.w * r.h * pix);
     size_t pitch = 0;
     for (auto &e : tab) pitch = std::max(pitch, (size_t)e.size);
     pitch = (pitch + 3) / 4 * 4;
     // containers at a fixed pitch on the device; the handle is parsed from tile 0 (tiles of another kind -- raw-stored
-    // ones -- are found and decoded on their own by qb3x_decode_tiles)
-    DevMem d_src(n * pitch), d_dst(n * raw);
+    // ones -- are found and decoded on their own by qb3x_decode_mosaic)
+    DevMem d_src(n * pitch), d_dst(r.px.size());
     if (!d_src.p || !d_dst.p) return fail("out of device memory");
     std::vector<size_t> sizes(n);
     for (size_t k = 0; k < n; k++) {
@@ -185,7 +179,7 @@ int decode(const std::string &in, const std::string &out, bool verbose) {
     decsp d = qb3_read_start(f.data() + tab[0].off, tab[0].size, dims);
     if (!d || !qb3_read_info(d) || dims[0] != T || dims[1] != T || dims[2] != h.bands) { if (d) qb3_destroy_decoder(d); return fail("tile 0 does not parse"); }
     const double t0 = now();
-    const size_t done = qb3x_decode_tiles(d, d_src.p, n, pitch, sizes.data(), d_dst.p, raw, nullptr, nullptr);
+    const size_t done = qb3x_decode_mosaic(d, d_src.p, pitch, sizes.data(), r.w, r.h, d_dst.p, 0, nullptr, nullptr);
     const double t1 = now();
     if (done != n) {
         std::string bad;
@@ -194,17 +188,7 @@ int decode(const std::string &in, const std::string &out, bool verbose) {
         return fail("tiles that did not decode:" + bad);
     }
     qb3_destroy_decoder(d);
-    std::vector<uint8_t> tiles(n * raw);
-    if (hipMemcpy(tiles.data(), d_dst.p, tiles.size(), hipMemcpyDeviceToHost) != hipSuccess) return fail("download failed");
-    Raster r;
-    r.w = h.w; r.h = h.h; r.bands = h.bands; r.type = (int)h.dtype;
-    r.px.resize(r.w * r.h * pix);
-    for (size_t j = 0; j < h.ty; j++)
-        for (size_t i = 0; i < h.tx; i++) {
-            const uint8_t *t = tiles.data() + (j * h.tx + i) * raw;
-            const size_t x0 = i * T, nx = x0 + T <= r.w ? T : r.w - x0;
-            for (size_t y = 0; y < T && j * T + y < r.h; y++) memcpy(r.px.data() + ((j * T + y) * r.w + x0) * pix, t + y * T * pix, nx * pix);
-        }
+    if (hipMemcpy(r.px.data(), d_dst.p, r.px.size(), hipMemcpyDeviceToHost) != hipSuccess) return fail("download failed");
     const bool pnm = (r.bands == 1 || r.bands == 3) && (r.type == QB3_U8 || r.type == QB3_U16);
     if (!(pnm ? write_pnm(out, r) : write_file(out, r.px.data(), r.px.size()))) return fail("cannot write " + out);
     if (verbose) printf("%zu tiles of %zu^2 decoded in %.2f ms (%.1f MPixel/s), %zu x %zu x %zu written%s\n", n, T, 1e3 * (t1 - t0), n * T * T / (t1 - t0) / 1e6,
