@@ -315,6 +315,49 @@ size_t qb3x_decode_mosaic(decsp p, const void *d_src, size_t src_pitch, const si
                           size_t W, size_t H, void *d_raster, size_t raster_stride,
                           const void *d_index, void *stream);
 
+/* Mosaic windows: rectangles of a mosaic's RASTER -- a viewport, a training crop, a reprojection's footprint -- from the tiles that
+ * hold them, in one call, whatever their relation to the tile grid.
+ *
+ * qb3x_mosaic_window_tiles is pure geometry (no device): the number of tiles of the qb3x_mosaic_tiles grid that hold a pixel of the
+ * rectangle [x0, x0 + w) x [y0, y0 + h); *i0 .. *i1 and *j0 .. *j1 (each may be NULL) receive the tile columns and rows, both ends
+ * included.  0 when the rectangle is empty or not inside W x H, or when W, H, tw or th is 0.
+ *
+ * qb3x_decode_mosaic_windows: p, d_src, src_pitch and sizes exactly as qb3x_decode_mosaic takes them (p parsed from tile 0, tile
+ * k = j * tx + i at d_src + k * src_pitch).  wins is a HOST array of n rectangles in raster pixels with DEVICE destinations;
+ * dst_stride is in values, 0 meaning w * bands.  Returns the number of windows written.
+ * Bytes: window i receives the crop [x0, x0 + w) x [y0, y0 + h) of what qb3x_decode_mosaic with the same p, d_src, src_pitch,
+ * sizes, W, H (and d_index NULL) writes into a W x H raster -- for every container, tile shape, handle setting (compat flags,
+ * quanta, band map, scan order, qb3x_set_decoder_window_kernels) and mix of tile kinds -- and no byte outside the window's h runs
+ * of w * bands values.  A window that holds a pixel of a tile that fails to decode is not ok and its content is unspecified; the
+ * other windows are unaffected.  Destinations must not overlap (not checked).
+ * Errors are decided before anything is launched or written, 0 returned: everything qb3x_decode_mosaic refuses for p, d_src,
+ * src_pitch, sizes, W, H; wins == NULL, n == 0, n > 2^20; ANY window that is empty, not inside W x H, has dst == NULL or a nonzero
+ * stride below w * bands (one bad window refuses the batch); more than 2^20 pieces in total, a PIECE being the part of one
+ * window that lies in one tile (the sum of qb3x_mosaic_window_tiles over the windows).
+ * Every piece takes one of two routes:
+ *   kernel  tile 0's handle is one path 1 takes without a switch (8-bit, 1 / 3 / 4 bands, FTL / BASE, a level-2 table, quanta 1)
+ *           and the piece's tile has tile 0's mode byte, and its "ix" tag and "DT" mark where tile 0 has them: the pieces of ALL
+ *           windows go up as one descriptor array and ONE launch decodes them from their containers, straight into the windows
+ *           (profile name dec_window_mosaic); one status copy and one synchronisation of `stream`.  The launch itself asks
+ *           whether a tile is of tile 0's kind and checks, tile by tile, the table chunks the pieces read entries from, the
+ *           table's last chunk and its end against that tile's size: a tile that fails sends all its pieces the other way, a
+ *           piece whose own segments raise a status sends that piece alone.  A damaged table costs time, never pixels.
+ *   whole   every other piece -- other value sizes, band counts and modes, RLE and raw-stored tiles, narrow tiles, handles
+ *           with quanta, tiles unlike tile 0, what failed above: the touched tiles that need it, and no others, are decoded
+ *           whole into memory of the handle's as qb3x_decode_tiles decodes them (consecutive tiles in one set of launches), each
+ *           at most once a call however many windows touch it, and ONE launch (mosaic_crop) copies the pieces out.
+ * Copies to the host and host loops follow the touched tiles, not the mosaic's tile count.
+ * Afterwards qb3x_window_ok(p, i) keeps its meaning; qb3x_window_path(p, i) is 1 when every piece of window i came from the
+ * window kernel, 3 when at least one came from a whole-tile decode, 0 when it failed; qb3x_last_window_path is the path of the
+ * last window; qb3x_last_window_segments counts the index segments the window kernel decoded (the sum of qb3x_window_segments
+ * over the pieces that went up, each in its tile); qb3x_last_mosaic_whole_tiles counts the tiles the call decoded whole.
+ * qb3x_decode_tile_ok keeps what the last tile or mosaic call left. */
+size_t qb3x_mosaic_window_tiles(size_t W, size_t H, size_t tw, size_t th, size_t x0, size_t y0, size_t w, size_t h,
+                                size_t *i0, size_t *j0, size_t *i1, size_t *j1);
+size_t qb3x_decode_mosaic_windows(decsp p, const void *d_src, size_t src_pitch, const size_t *sizes,
+                                  size_t W, size_t H, const qb3x_window *wins, size_t n, void *stream);
+size_t qb3x_last_mosaic_whole_tiles(const decsp p);
+
 /* qb3_read_start for the device flavour: `header` is a host copy of the FIRST header_size bytes of a container of
  * stream_size bytes (the parser never reads beyond the copy; qb3_read_info fails when the copy ends before the
  * container's "DT" mark).  qb3x_header_size_bound(first bytes, how many) says how many bytes always suffice,

@@ -99,6 +99,9 @@ _PROTOS = {
     "qb3x_mosaic_tiles": (_sz, [_sz, _sz, _sz, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
     "qb3x_encode_mosaic": (_sz, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp, C.POINTER(_sz), _vp]),
     "qb3x_decode_mosaic": (_sz, [_vp, _vp, _sz, C.POINTER(_sz), _sz, _sz, _vp, _sz, _vp, _vp]),
+    "qb3x_mosaic_window_tiles": (_sz, [_sz] * 8 + [C.POINTER(_sz)] * 4),
+    "qb3x_decode_mosaic_windows": (_sz, [_vp, _vp, _sz, C.POINTER(_sz), _sz, _sz, _vp, _sz, _vp]),
+    "qb3x_last_mosaic_whole_tiles": (_sz, [_vp]),
     "qb3x_decode_window_device": (_sz, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp]),
     "qb3x_read_window": (_sz, [_vp, _sz, _sz, _sz, _sz, _vp, _sz]),
     "qb3x_window_segments": (_sz, [_vp, _sz, _sz, _sz, _sz, C.POINTER(_sz)]),

@@ -24,7 +24,8 @@ void win_u8_batch(const Geometry &g, const DecPlan &plan, const WinBatchArgs &ba
 }
 // 8-bit grey / RGB / RGBA rasters, FTL / BASE: dec_px_kernel's BL branch a segment, byte and dword stores to any address
 const WinKernels &win_u8() {      // (in a function: host data, not for the device side of this file)
-    static const WinKernels k = { decode_window_ok, 0, window_align_any, nullptr, window_lds_px, "", "dec_window", "dec_window_ranged", win_u8_one, win_u8_batch, win_u8_ranged };
+    static const WinKernels k = { decode_window_ok, 0, window_align_any, nullptr, window_lds_px, "", "dec_window", "dec_window_ranged", win_u8_one, win_u8_batch, win_u8_ranged,
+                                  nullptr, win_u8_mosaic, "dec_window_mosaic" };
     return k;
 }
 

@@ -813,7 +813,8 @@ size_t qb3api::decode_common(decsp p, void *host_dst, const void *d_src, void *d
         const uint8_t *s = t.data();
         if (p->xsize < 4) for (size_t y = 0; y < p->ysize; y++, s += p->xsize * pix) memcpy(dst + y * dst_stride, s, p->xsize * pix);
         else for (size_t x = 0; x < p->xsize; x++) for (size_t y = 0; y < p->ysize; y++, s += pix) memcpy(dst + y * dst_stride + x * pix, s, pix);
-        if (!on_host) { HIPOK(hipMemcpyAsync(d_dst, dst, outimg.size(), hipMemcpyHostToDevice, st)); HIPOK(hipStreamSynchronize(st)); }
+        // (row by row: the gaps of a wide stride are not the image's -- in a mosaic they are the neighbouring tiles)
+        if (!on_host) { HIPOK(hipMemcpy2DAsync(d_dst, dst_stride, dst, dst_stride, p->xsize * pix, p->ysize, hipMemcpyHostToDevice, st)); HIPOK(hipStreamSynchronize(st)); }
         return total;
     }
     if (on_host) {

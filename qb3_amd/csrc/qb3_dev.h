@@ -311,7 +311,7 @@ int launch_window_tail_check(const Geometry &g, uint64_t in_bits, uint32_t *stat
 // Each family has up to three FORMS, one kernel shell each (qb3_win.h): a single window as kernel arguments, a batch of windows from a
 // descriptor array, a batch decoded from fetched pieces of the container (ranged).  A dispatcher launches the shell's instantiation
 // that the geometry and the plan select.
-struct DecArgs; struct WinArgs; struct WinBatchArgs; struct WinRangedArgs;      // (qb3_kernels.h, qb3_win.h)
+struct DecArgs; struct WinArgs; struct WinBatchArgs; struct WinRangedArgs; struct WinMosaicArgs;      // (qb3_kernels.h, qb3_win.h)
 struct WinLaunch { uint32_t grid; size_t lds; void *stream; };
 struct WinKernels {
     bool (*ok)(const Geometry &, const DecPlan &, const IxTable &);     // does the raster and its table qualify
@@ -324,6 +324,8 @@ struct WinKernels {
     void (*batch)(const Geometry &, const DecPlan &, const WinBatchArgs &, const WinLaunch &);
     void (*ranged)(const Geometry &, const DecPlan &, const WinRangedArgs &, const WinLaunch &);    // null: the family has no ranged form
     void (*batch_sel)(const Geometry &, const DecPlan &, const WinBatchArgs &, const WinLaunch &);  // the batch form that writes selected bands only (null: the family has none)
+    void (*mosaic)(const Geometry &, const DecPlan &, const WinMosaicArgs &, const WinLaunch &);    // a batch over the tiles of a mosaic, a container a piece (null: the family has none)
+    const char *prof_mosaic;                                                                        // ... its profile name
 };
 const WinKernels &win_u8(), &win_u16(), &win_cf8(), &win_unit(), &win_cfu();
 bool decode_window_ok(const Geometry &g, const DecPlan &plan, const IxTable &ix);        // win_u8's predicate (k_dec_win.hip)
@@ -373,6 +375,27 @@ constexpr size_t WIN_PIECE_BYTES = 32;
 int launch_decode_windows_ranged(const WinKernels &k, const Geometry &g, const DecPlan &plan, uint32_t in_bit0, uint64_t in_bits, const void *h_descs,
                                  const void *d_descs, size_t n, const void *d_pieces, size_t npieces, const void *d_entries, const uint32_t *d_words,
                                  uint32_t *d_status, void *stream, const IxTable &ix);
+
+// Mosaic windows (k_dec_wins_mosaic.hip, api_mosaic_windows.cpp): the batch form over MANY containers of one shape -- the tiles of a mosaic.
+// A descriptor is a PIECE, the part of a window that lies in one tile, in that tile's coordinates (window_desc; its destination already
+// where the piece lies in its window), and names its tile in the descriptor's spare dword: an index into an array of WinTile in device
+// memory, from which the wave takes the three things that differ between tiles -- where the stream starts, how long it is, where the
+// table is.  Geometry, the table's shape and in_bit0 are those of tile 0 for every tile.  The launch's first nchecks workgroups check
+// one table chunk of one tile each (WinTileCheck; the entry of a tile's LAST chunk has WIN_TILE_TAIL set: its workgroup also makes the
+// tail check against that tile's stream length and compares the tile's mode byte, "ix" tag and "DT" mark with tile 0's: mode_byte at
+// byte 10 of the container, the tag ix_off bytes in, the mark in front of byte hdr).  d_status: 1 + n + ntiles zeroed words -- word 0 is
+// not written, word 1 + i is piece i's, word 1 + n + t is tile t's (a failed check).  The descriptors' wave0 prefixes start again where a
+// launch would exceed WIN_LAUNCH_WAVES, as window_batch_plan's do.  Does not synchronise.  Returns hipError_t as int.
+struct WinTile { const uint32_t *in32; uint64_t in_bits; const uint8_t *ix; uint64_t pad_; };
+struct WinTileCheck { uint32_t tile, chunk; };
+constexpr size_t WIN_TILE_BYTES = 32, WIN_TILE_CHECK_BYTES = 8;
+constexpr uint32_t WIN_TILE_TAIL = 1u << 31;
+// fills n piece descriptors of WIN_DESC_BYTES each at `descs` (host memory that goes up as it is): piece i is rects[i] of tile record
+// tiles[i], written to dsts[i]; *segments: the sum of the pieces' segment counts
+void window_mosaic_plan(const Geometry &g, const WinRect *rects, void *const *dsts, const uint32_t *tiles, size_t n, void *descs, uint64_t *segments);
+int launch_decode_windows_mosaic(const WinKernels &k, const Geometry &g, const DecPlan &plan, uint32_t in_bit0, const void *h_descs, const void *d_descs,
+                                 size_t n, const void *d_tiles, size_t ntiles, const void *d_checks, size_t nchecks, uint32_t *d_status, void *stream,
+                                 const IxTable &ix, uint32_t ix_off, uint32_t hdr, uint32_t mode_byte);
 
 // Mosaics (k_mosaic.hip): the tiles that cross a raster's right or bottom edge are coded from, and decoded into, memory of the handle's.
 // One descriptor a tile and ONE launch for n of them copies the rows of a rectangle and, where the destination is larger, repeats the

@@ -127,7 +127,8 @@ struct decs {
     DevBuf d_wfull, d_wgat;                            // band-selected windows (api_window_bands.cpp): full-band windows a window kernel wrote for the gather; the gather's descriptors
     PinBuf h_wgat;                                     // ... their pinned host copy
     size_t win_gathers = 0;                            // ... gather launches of the last band-selected call (qb3x_last_window_gathers)
-    DevBuf d_mos;                                      // qb3x_decode_mosaic: the edge tiles' descriptors and the whole tiles they decode to
+    DevBuf d_mos;                                      // qb3x_decode_mosaic: the edge tiles' descriptors and the whole tiles they decode to; qb3x_decode_mosaic_windows: the same for the tiles it decodes whole
+    size_t mos_whole = 0;                              // ... tiles the last qb3x_decode_mosaic_windows decoded whole (qb3x_last_mosaic_whole_tiles)
     Stager stager, stager2;                            // (stager2: the download ring of a pipelined host call)
     Pipe pipe;                                         // ... its streams and events
     // a ranged handle (qb3x_open_ranged, api_ranged.cpp): the caller's reader, the container's size, what the last call asked of the reader

@@ -1,6 +1,7 @@
 // qb3_amd/csrc/qb3_win.h -- what the window kernels of every family share (qb3_dev.h lists the families): the per-window numbers, the
 // arguments and the split of a batch into launches, the two sources a wave reads from, the check of the table's end, and -- at the
-// end -- the three kernel SHELLS, one per form, that every family instantiates over its wave routine.  Then the 8-bit family's own:
+// end -- the kernel SHELLS, one per form, that every family instantiates over its wave routine (three every family has, and the mosaic
+// shell, which a family has once it is instantiated for it: the 8-bit one, k_dec_wins_mosaic.hip).  Then the 8-bit family's own:
 // the wave's work (a segment decoded from its table entry, its blocks clipped to the window and stored) and its instantiations.
 // The comment at the head of k_dec_win.hip describes mapping, clipping and trust.
 #pragma once
@@ -149,7 +150,7 @@ struct WinRangedArgs {
     uint32_t nwin;
 };
 
-// The three SHELLS: what surrounds a family's wave routine in each form.  F names one instantiation of a family (WinU8 below, Win16,
+// The SHELLS (the mosaic one stands with its arguments, further down): what surrounds a family's wave routine in each form.  F names one instantiation of a family (WinU8 below, Win16,
 // WinCf8, WinUnit, WinCfu next to their wave routines): F::contig and F::pieces are the routine with the instantiation's template
 // arguments over the two sources, F::waves is the second number of the launch bounds (0: none given, the attributes are those of
 // __launch_bounds__(256)).  The two are constants of function type, so a shell calls the routine itself: with a forwarding function
@@ -213,6 +214,50 @@ __global__ void __launch_bounds__(256, F::waves) win_ranged_kernel(const WinRang
     const uint32_t i = win_search(ra.wins, ra.nwin, gw);
     const WinDesc w = ra.wins[i];
     F::pieces(ra.d, w, ra.wstatus + i, smem, wave, gw - w.wave0, ra.src);
+}
+// What the mosaic shell takes (win_mosaic_kernel): a batch whose windows are PIECES, each in a container of its own (qb3_dev.h, "Mosaic windows")
+struct WinMosaicArgs {
+    DecArgs d;                      // tile 0's: geometry, table shape, in_bit0, staging capacity; d.in32, d.in_bits, d.ix and d.status are not used
+    const WinDesc *wins;            // the launch's pieces, wave0 counted from the launch's first piece; pad_: the piece's tile
+    uint32_t *wstatus;              // ... their status words
+    const WinTile *tiles;           // stream, stream length and table of every tile a piece names
+    uint32_t *tstatus;              // ... their status words (a failed check)
+    const WinTileCheck *checks;     // (tile, table chunk) pairs to check, chk_n of them (the first launch of a call only)
+    uint32_t nwin, chk_n;
+    uint32_t ix_off, mode_byte;     // tile 0's: offset of the first "ix" chunk in a container, the mode byte
+};
+// A batch over many containers of one shape: the batch shell with the three fields of DecArgs that differ between tiles taken from the
+// piece's tile, in a LOCAL copy of the arguments (DecArgs does not grow for it).  The piece's tile number and the tile's record are wave
+// uniform: scalar loads.
+// (Launch bounds: a family that gives none gets 8 waves a SIMD here.  Left to itself the compiler takes 69 vector registers and 7 waves for
+// the 8-bit family where the batch shell has 64 and 8; asked for 8 it needs 53 to 62 and no scratch.)
+template <class F>
+__global__ void __launch_bounds__(256, F::waves ? F::waves : 8) win_mosaic_kernel(const WinMosaicArgs ma) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    if (blockIdx.x < ma.chk_n) {                        // the launch's first workgroups: a chunk of one tile's table each
+        const WinTileCheck c = ma.checks[blockIdx.x];
+        const WinTile t = ma.tiles[c.tile];
+        DecArgs a = ma.d;
+        a.in32 = t.in32; a.in_bits = t.in_bits; a.ix = t.ix; a.status = ma.tstatus + c.tile;
+        // (with check_heads on this also holds the tile to tile 0's "ix" tag at every chunk checked and to the "DT" mark behind the last)
+        ix_check_chunk(a, c.chunk & ~WIN_TILE_TAIL, (uint32_t *)smem);
+        if ((c.chunk & WIN_TILE_TAIL) && threadIdx.x == 0) {    // ... with the tile's last chunk: the table's end, and the one thing the chunks do not say -- the mode byte
+            ix_tail_check(a);
+            if ((t.ix - ma.ix_off)[10] != ma.mode_byte) atomicOr(a.status, 64u);
+        }
+        return;
+    }
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t gw = (blockIdx.x - ma.chk_n) * 4 + wave;
+    const uint32_t i = win_search(ma.wins, ma.nwin, gw);
+    const WinDesc w = ma.wins[i];                       // sixteen dwords, read before anything is stored
+    const WinTile t = ma.tiles[w.pad_];
+    DecArgs a = ma.d;
+    a.in32 = t.in32; a.in_bits = t.in_bits; a.ix = t.ix;
+    F::contig(a, w, ma.wstatus + i, smem, wave, gw - w.wave0, WinSrcContig());
+}
+template <class F> inline void win_launch(F, const WinMosaicArgs &ma, const WinLaunch &l) {
+    hipLaunchKernelGGL((win_mosaic_kernel<F>), dim3(l.grid), dim3(256), l.lds, (hipStream_t)l.stream, ma);
 }
 template <class F> inline void win_launch(F, const WinArgs &wa, const WinLaunch &l) {
     hipLaunchKernelGGL((win_one_kernel<F>), dim3(l.grid), dim3(256), l.lds, (hipStream_t)l.stream, wa);
@@ -439,5 +484,6 @@ inline void win_u8_pick(const Geometry &g, const DecPlan &plan, Visit visit) {
 void win_u8_one(const Geometry &g, const DecPlan &plan, const WinArgs &wa, const WinLaunch &l);
 void win_u8_batch(const Geometry &g, const DecPlan &plan, const WinBatchArgs &ba, const WinLaunch &l);
 void win_u8_ranged(const Geometry &g, const DecPlan &plan, const WinRangedArgs &ra, const WinLaunch &l);
+void win_u8_mosaic(const Geometry &g, const DecPlan &plan, const WinMosaicArgs &ma, const WinLaunch &l);
 
 }  // namespace qb3dev

@@ -342,6 +342,41 @@ class MosaicCoder:
             raise RuntimeError(f"qb3x_decode_mosaic decoded {k} of {self.n} tiles: {last_error()}")
         return out
 
+    def decode_windows(self, rects, out=None):
+        """rectangles (x0, y0, w, h) of the RASTER from the containers made by encode(), in one call (qb3x_decode_mosaic_windows).
+        Returns a list of (h, w, bands) tensors of the raster's type, views of one buffer; or fills `out`, a list of contiguous uint8
+        device tensors of at least h * w * bands * value size bytes each.  last_windows() then tells how each went."""
+        rects = [tuple(int(v) for v in r) for r in rects]
+        pix = self.bands * TYPESIZE[self.dtype]
+        sizes = [w * h * pix for (_, _, w, h) in rects]
+        if out is None:
+            offs = [0]
+            for nb in sizes:
+                offs.append(offs[-1] + (nb + 7) // 8 * 8)     # (every window on eight bytes: a view of any value type)
+            buf = torch.empty(max(offs[-1], 8), dtype=torch.uint8, device=self.dst.device)
+            out = [buf[offs[i]:offs[i] + sizes[i]] for i in range(len(rects))]
+        assert len(out) == len(rects)
+        for o, nb in zip(out, sizes):
+            assert o.is_cuda and o.is_contiguous() and o.dtype == torch.uint8 and o.numel() >= nb
+        if self.d is None:
+            dims = (_sz * 3)()
+            self.d = lib.qb3x_read_start_device(_vp(self.dst.data_ptr()), int(self.sizes[0]), dims, _stream_ptr())
+            if not self.d:
+                raise ValueError("tile 0 does not parse")
+        wins = window_array(rects, [o.data_ptr() for o in out])
+        n = lib.qb3x_decode_mosaic_windows(self.d, _vp(self.dst.data_ptr()), self.pitch, self.sizes, self.W, self.H, wins, len(rects), _stream_ptr())
+        self._nwin = len(rects)
+        if n != len(rects):
+            raise RuntimeError(f"qb3x_decode_mosaic_windows wrote {n} of {len(rects)} windows: {last_error()}")
+        return [o.view(-1)[:nb].view(getattr(torch, NP_DTYPE[self.dtype])).view(h, w, self.bands) for o, nb, (_, _, w, h) in zip(out, sizes, rects)]
+
+    def last_windows(self):
+        """of the last decode_windows: ([ok], [path], tiles decoded whole) -- path 1: every piece of the window came from the window
+        kernel, 3: at least one from a whole-tile decode, 0: not written"""
+        n = getattr(self, "_nwin", 0) if self.d else 0
+        return ([bool(lib.qb3x_window_ok(self.d, i)) for i in range(n)], [lib.qb3x_window_path(self.d, i) for i in range(n)],
+                lib.qb3x_last_mosaic_whole_tiles(self.d) if self.d else 0)
+
 
 def profile_enable(on=True):
     """True / 1: every kernel; 2: skip the microsecond kernels (less event traffic in a timed loop); 3: the coding kernels (`*_units`) alone; False / 0: off."""

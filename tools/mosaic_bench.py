@@ -9,7 +9,9 @@ bottom row); every tile's container carries its level-2 restart table, so both w
   ratio                  mosaic over tiles, of the minima;
   kernel_ms              per kernel, from the library's profile (ms a call), in a pass of its own for each way.
 Both ways are checked to write the same containers and to return the raster.  Without CASE every raster runs in a child process of its
-own under a time limit, and the first failure ends the run."""
+own under a time limit, and the first failure ends the run.
+--windows N --win WxH[,WxH...] times reads by rectangle instead (run_windows): N seeded random rectangles of each shape through
+qb3x_decode_mosaic_windows against the whole decode followed by slices and against a loop of per-tile window calls."""
 import json
 import os
 import statistics
@@ -104,12 +106,126 @@ def run(case, rounds=7):
     print(json.dumps(res), flush=True)
 
 
+def run_windows(case, nwin, shapes, rounds=7):
+    """--windows: nwin seeded random rectangles of each shape, read three ways from the containers of `case`:
+      mosaic_windows   qb3x_decode_mosaic_windows, one call;
+      decode_all       qb3x_decode_mosaic of everything, then the slices copied into the windows;
+      per_tile_loop    one qb3x_decode_windows_device call per touched tile, over that tile's pieces; the per-tile handles and the
+                       window arrays are made outside the timed region.
+    Events around each way, the ways alternating over the rounds of one process; one JSON line a shape."""
+    import ctypes as C
+    import numpy as np
+    import torch
+    import qb3_amd
+    from qb3_amd import synth, device as qdev
+    L = qb3_amd.lib
+    W, H = CASES[case]
+    raster = synth.generate(W, H, B, 0, "NOISY3", 3).reshape(H, W, B)
+    mc = qdev.MosaicCoder(W, H, B, 0, tile=(T, T), index_chunk=2)
+    mc.encode(raster)
+    out_m = torch.empty_like(raster)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    handles = {}
+    for (ww, wh) in shapes:
+        rng = np.random.default_rng(nwin * 1000003 + ww * 1009 + wh)
+        rects = [(int(rng.integers(0, W - ww + 1)), int(rng.integers(0, H - wh + 1)), ww, wh) for _ in range(nwin)]
+        outs = [torch.empty(ww * wh * B, dtype=torch.uint8, device="cuda") for _ in rects]
+        per_tile = {}                                       # tile -> [(x, y, w, h in the tile, destination, stride)]
+        for (x0, y0, w, h), o in zip(rects, outs):
+            for j in range(y0 // T, (y0 + h - 1) // T + 1):
+                for i in range(x0 // T, (x0 + w - 1) // T + 1):
+                    ax, bx, ay, by = max(x0, i * T), min(x0 + w, (i + 1) * T), max(y0, j * T), min(y0 + h, (j + 1) * T)
+                    per_tile.setdefault(j * mc.tx + i, []).append((ax - i * T, ay - j * T, bx - ax, by - ay,
+                                                                   o.data_ptr() + ((ay - y0) * w + (ax - x0)) * B, w * B))
+        calls = []
+        for k, ps in sorted(per_tile.items()):
+            if k not in handles:
+                dims = (C.c_size_t * 3)()
+                handles[k] = L.qb3x_read_start_device(C.c_void_p(mc.dst.data_ptr() + k * mc.pitch), int(mc.sizes[k]), dims, stream)
+                assert handles[k], "tile %d does not parse" % k
+            arr = qb3_amd.window_array([p[:4] for p in ps], [p[4] for p in ps], [p[5] for p in ps])
+            calls.append((handles[k], C.c_void_p(mc.dst.data_ptr() + k * mc.pitch), arr, len(ps)))
+
+        mc.decode_windows(rects[:1], out=outs[:1])         # (parses tile 0: the handle is made outside the timed region, as the loop's are)
+        wins = qb3_amd.window_array(rects, [o.data_ptr() for o in outs])
+        src0 = C.c_void_p(mc.dst.data_ptr())
+
+        def mosaic_windows():                               # the window array prebuilt too, as the loop's
+            if L.qb3x_decode_mosaic_windows(mc.d, src0, mc.pitch, mc.sizes, W, H, wins, nwin, stream) != nwin:
+                raise RuntimeError("qb3x_decode_mosaic_windows: " + qb3_amd.last_error())
+
+        def decode_all():
+            mc.decode(out_m)
+            for (x0, y0, w, h), o in zip(rects, outs):
+                o.view(h, w, B).copy_(out_m[y0:y0 + h, x0:x0 + w])
+
+        def per_tile_loop():
+            for (p, src, arr, n) in calls:
+                if L.qb3x_decode_windows_device(p, src, None, arr, n, stream) != n:
+                    raise RuntimeError("qb3x_decode_windows_device: " + qb3_amd.last_error())
+
+        ways = {"mosaic_windows": mosaic_windows, "decode_all": decode_all, "per_tile_loop": per_tile_loop}
+        for name, fn in ways.items():                       # warm-up, and the check that every way returns the raster's crops
+            for o in outs:
+                o.fill_(0xA5)
+            fn()
+            torch.cuda.synchronize()
+            for (x0, y0, w, h), o in zip(rects, outs):
+                assert torch.equal(o.view(h, w, B), raster[y0:y0 + h, x0:x0 + w]), "%s: window (%d, %d)" % (name, x0, y0)
+        mosaic_windows()
+        paths = [L.qb3x_window_path(mc.d, i) for i in range(nwin)]
+        whole = L.qb3x_last_mosaic_whole_tiles(mc.d)
+        t = {k: [] for k in ways}
+        for _ in range(rounds):
+            for k, fn in ways.items():
+                t[k].append(timed(fn))
+        kern = {}
+        for name in ("mosaic_windows", "per_tile_loop"):
+            qdev.profile_reset()
+            qdev.profile_enable(1)
+            for _ in range(2):
+                ways[name]()
+            torch.cuda.synchronize()
+            qdev.profile_enable(0)
+            kern[name] = {k: [round(v[0] / 2, 4), v[1] // 2] for k, v in sorted(qdev.profile_report().items())}     # [ms, launches] a call of the way
+        stat = lambda v: {"min": round(min(v), 3), "median": round(statistics.median(v), 3)}
+        res = {"mode": "windows", "case": case, "raster": [W, H, B], "tile": T, "tiles": mc.n, "windows": nwin, "win": [ww, wh],
+               "pieces": sum(len(v) for v in per_tile.values()), "touched_tiles": len(per_tile), "rounds": rounds,
+               "paths": sorted(set(paths)), "whole_tiles": whole}
+        for k in ways:
+            res[k + "_ms"] = stat(t[k])
+        res["ratio_to_decode_all"] = round(min(t["mosaic_windows"]) / min(t["decode_all"]), 4)
+        res["ratio_to_per_tile_loop"] = round(min(t["mosaic_windows"]) / min(t["per_tile_loop"]), 4)
+        res["kernel_ms"] = kern
+        print(json.dumps(res), flush=True)
+    for p in handles.values():
+        L.qb3_destroy_decoder(p)
+    mc.close()
+
+
+def window_args(args):
+    """--windows N --win WxH[,WxH...] taken out of args: (N, [(W, H)], the rest)"""
+    nwin, shapes, rest = 0, [], []
+    it = iter(args)
+    for a in it:
+        if a == "--windows":
+            nwin = int(next(it))
+        elif a == "--win":
+            shapes = [tuple(int(v) for v in s.split("x")) for s in next(it).split(",")]
+        else:
+            rest.append(a)
+    if bool(nwin) != bool(shapes):
+        sys.exit("mosaic_bench: --windows N and --win WxH go together")
+    return nwin, shapes, rest
+
+
 if __name__ == "__main__":
-    args = sys.argv[1:]
+    nwin, shapes, args = window_args(sys.argv[1:])
     if args:
-        run(args[0])
+        run_windows(args[0], nwin, shapes) if nwin else run(args[0])
     else:
+        extra = ["--windows", str(nwin), "--win", ",".join("%dx%d" % s for s in shapes)] if nwin else []
         for case in CASES:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), case], timeout=280)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), case] + extra, timeout=280)
             if r.returncode:
                 sys.exit("mosaic_bench: %s ended with status %d; nothing more is run" % (case, r.returncode))
