@@ -1,12 +1,12 @@
 """What the tests of the 16-bit window kernels share (test_window16_plan.py, test_window16_decode.py): the shapes, the generators,
-the windows every raster is asked for, the rungs of a raster's units restated in numpy, and the seal of a table chunk."""
+the windows every raster is asked for, and the rungs of a raster's units restated in numpy.  The device plumbing is
+qb3_window_dev.py's."""
 import numpy as np
 
 import qb3_window as W
+from qb3_window_dev import QB3X_WINK_U16, U16, I16  # noqa: F401
 
-QB3X_WINK_U16 = 1
 HILBERT = 0x01548CD9AEFB7623            # reference QB3common.h:193
-U16, I16 = 2, 3
 
 # the smallest shapes at which each mechanism can fail, by blocks per row (nbx) against blocks per segment (NB: 64 for 1..4 bands,
 # 32 for eight bands, 21 for six -- 64 / band groups)
@@ -50,11 +50,3 @@ def unit_rungs(band):
     d = ((d + 32768) & 0xffff) - 32768                                      # the difference as a 16-bit two's complement number
     m = np.where(d < 0, -2 * d - 1, 2 * d).reshape(-1, 16).max(axis=1)
     return np.floor(np.log2(np.maximum(m, 1))).astype(np.int64)
-
-
-def seal(entry_bytes):
-    """the 16-bit check of a version 3 "ix" chunk over its entry bytes (include/qb3x.h)"""
-    b = np.asarray(entry_bytes, dtype=np.uint64)
-    i = np.arange(len(b), dtype=np.uint64)
-    s = int((((b + 1) * ((i * 0x9e3779b1 + 1) & 0xffffffff)) & 0xffffffff).sum()) & 0xffffffff
-    return (s ^ (s >> 16)) & 0xffff

@@ -1,13 +1,14 @@
 """What the tests of the band-selected window calls share (test_window_bands_plan.py, test_window_bands_decode.py): the selections of a
 band count, the expected bytes -- always the SOURCE raster (or a second handle's whole decode) with the bands picked, never a window
-call's -- and the sentinel-guarded destinations, which are qb3_window_unit's with `nsel` values a pixel in place of the band count."""
+call's -- and the sentinel-guarded destinations, which are qb3_window_dev's "unit" layout with `nsel` values a pixel in place of the
+band count."""
 import ctypes as C
 
 import numpy as np
 
-import qb3_window_unit as WU
+import qb3_window_dev as D
 
-SENTINEL = WU.SENTINEL
+SENTINEL = D.SENTINEL
 _vp = C.c_void_p
 NAMES = ("qb3x_decode_windows_bands_device", "qb3x_read_windows_bands", "qb3x_last_window_gathers")
 
@@ -34,11 +35,11 @@ def select(rows, bands, tsz, sel):
     return px.contiguous() if hasattr(px, "contiguous") else np.ascontiguousarray(px)
 
 
-class Layout(WU.Layout):
-    """WU.Layout with nsel values a pixel; shift: every destination that many BYTES further on (1: off value alignment)"""
+class Layout(D.Layout):
+    """the "unit" layout with nsel values a pixel; shift: every destination that many BYTES further on (1: off value alignment)"""
 
     def __init__(self, rects, nsel, tsz, mosaic=None, shift=0):
-        super().__init__(rects, nsel * tsz, tsz, mosaic)
+        super().__init__(rects, nsel * tsz, tsz, "unit", mosaic)
         self.offs = [o + shift for o in self.offs]
         self.size += shift
 
@@ -54,10 +55,9 @@ def bands_call(qb3, dec, d_c, lay, sel, host=None, index=None):
         wins = qb3.window_array(lay.rects, [hbuf.ctypes.data + base + o for o in lay.offs], lay.strides())
         n = qb3.lib.qb3x_read_windows_bands(host, wins, len(lay.rects), arr, len(sel))
         return n, torch.from_numpy(hbuf[base:base + lay.size]).cuda()
-    buf = torch.full((lay.size,), SENTINEL, dtype=torch.uint8, device="cuda")
+    buf = lay.buffer()
     assert buf.data_ptr() % 16 == 0
-    wins = qb3.window_array(lay.rects, [buf.data_ptr() + o for o in lay.offs], lay.strides())
-    n = qb3.lib.qb3x_decode_windows_bands_device(dec.p, _vp(d_c.data_ptr()), _vp(index.data_ptr()) if index is not None else None, wins, len(lay.rects),
+    n = qb3.lib.qb3x_decode_windows_bands_device(dec.p, _vp(d_c.data_ptr()), _vp(index.data_ptr()) if index is not None else None, lay.array(qb3, buf), len(lay.rects),
                                                  arr, len(sel), _vp(torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
     return n, buf

@@ -46,6 +46,11 @@ def raster(generate, name, w, h, b, seed):
     return mixed(w, h, b, seed)
 
 
+def device_raster(oracle, name, Wd, Ht, bands, seed):
+    import torch
+    return torch.from_numpy(raster(oracle.generate, name, Wd, Ht, bands, seed)).cuda()
+
+
 def entry_bytes(bands):
     """a table entry of these rasters: 6 position bytes, a rung, an entering value and a factor per band, 64 fields of 3 bytes"""
     return 6 + 3 * bands + 192

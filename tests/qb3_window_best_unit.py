@@ -1,7 +1,7 @@
 """What the tests of the window kernels of the remaining common-factor rasters share (test_window_best_unit_plan.py,
 test_window_best_unit_decode.py): the (type, bands) matrix, rasters of any integer type that reach every unit form of a common-factor
-stream, and the fields of a table entry.  Shapes, band maps and the device plumbing are qb3_window_unit's, the patchwork is
-qb3_window_best's in the value's width."""
+stream, and the fields of a table entry.  Shapes and band maps are qb3_window_unit's, the device plumbing is qb3_window_dev's, the
+patchwork is qb3_window_best's in the value's width."""
 import numpy as np
 
 import qb3_window_unit as WU

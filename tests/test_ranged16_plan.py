@@ -12,8 +12,8 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import qb3_ranged as R  # noqa: E402
-import qb3_ranged16 as R16  # noqa: E402
 import qb3_window16 as W16  # noqa: E402
+from qb3_window_dev import chunk_check  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FTL, BASE = 8, 4
@@ -39,7 +39,7 @@ def with_table(c, E, blocks, W_, H_, version=3, flags=2):
         for j in range(here):
             body[j * E:j * E + 6] = (1000 * (k0 + j)).to_bytes(6, "little")
             body[j * E + 6:j * E + E] = bytes((7 * (k0 + j) + i) & 0xff for i in range(E - 6))
-        chk = R.chunk_check(body)
+        chk = chunk_check(body)
         run += b"ix" + bytes([ln & 255, ln >> 8, version, flags, chk & 255, chk >> 8]) + blocks.to_bytes(4, "little") + body + b"zz\x04\x00"
     return np.concatenate([c[:at], np.frombuffer(bytes(run), np.uint8), c[at:]])
 
@@ -55,13 +55,13 @@ def table_ranges(qb3, p, rects):
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "%dx%dx%d" % (c[1], c[2], c[0]))
 def test_table_ranges_follow_the_rule_with_the_rasters_segment_size(qb3, oracle, case):
     """without the bit: nothing is planned (a 16-bit raster is read whole); with it: the chunk ranges of the rule restated in
-    qb3_ranged16.py, for single rectangles and for batches that share chunks; a bad rectangle plans nothing; no read at all"""
+    qb3_ranged.py, for single rectangles and for batches that share chunks; a bad rectangle plans nothing; no read at all"""
     L = qb3.lib
     bands, Wd, Ht = case
     dt = I16 if case == (4, 260, 37) else U16
-    E, B = R16.entry_bytes(bands), R16.blocks_per_segment(bands)
+    E, B = R.entry_bytes("u16", bands), R.blocks_per_segment("u16", bands)
     c = with_table(oracle.encode(oracle.generate(Wd, Ht, bands, dt, "LANDSAT16", 2), dt, FTL if bands != 6 else BASE), E, B, Wd, Ht)
-    tab = R16.Table(c).shape(E)
+    tab = R.Table(c).shape(E)
     src = R.Source(qb3, c)
     p, dims = src.open(qb3)
     assert p and dims == (Wd, Ht, bands) and L.qb3x_decoder_table_entries(p) == tab.K
@@ -71,17 +71,17 @@ def test_table_ranges_follow_the_rule_with_the_rasters_segment_size(qb3, oracle,
     L.qb3x_set_decoder_window_kernels(p, BIT)
     seen = set()
     for r in rects:
-        want = [tab.chunk_range(k) for k in R16.plan_chunks(Wd, Ht, [r], tab.K, tab.N, B)]
+        want = [tab.chunk_range(k) for k in R.plan_chunks(Wd, Ht, [r], tab.K, tab.N, B)]
         assert want and table_ranges(qb3, p, [r]) == want, r
         seen.add(len(want))
     if case == (8, 1000, 520):
         assert tab.K == 1016 and len(tab.chunks) == 3 and seen == {1, 2, 3}
         assert tab.chunk_range(2)[0] + tab.chunk_range(2)[1] == tab.D
     for batch in (rects, rects[1:5], rects[5:], rects[::3]):
-        assert table_ranges(qb3, p, batch) == [tab.chunk_range(k) for k in R16.plan_chunks(Wd, Ht, batch, tab.K, tab.N, B)]
+        assert table_ranges(qb3, p, batch) == [tab.chunk_range(k) for k in R.plan_chunks(Wd, Ht, batch, tab.K, tab.N, B)]
     wins = qb3.window_array(rects, [0] * len(rects))
     one = (qb3.Range * 1)()
-    assert L.qb3x_ranged_table_ranges(p, wins, len(rects), one, 1) == len(R16.plan_chunks(Wd, Ht, rects, tab.K, tab.N, B))
+    assert L.qb3x_ranged_table_ranges(p, wins, len(rects), one, 1) == len(R.plan_chunks(Wd, Ht, rects, tab.K, tab.N, B))
     assert (int(one[0].offset), int(one[0].size)) == tab.chunk_range(0)
     assert table_ranges(qb3, p, [(0, 0, Wd + 1, 1)]) == [] and table_ranges(qb3, p, [(0, 0, 0, 1)]) == []
     assert table_ranges(qb3, p, [rects[0], (0, 0, Wd + 1, 1)]) == []
@@ -114,13 +114,13 @@ def test_the_bit_changes_nothing_for_rasters_the_kernels_do_not_take(qb3, oracle
 
     E8 = 6 + 2 * 3 + 80
     c = with_table(oracle.encode(oracle.generate(Wd, Ht, 3, 0, "NOISY3", 2), 0, FTL), E8, 64, Wd, Ht)
-    tab = R.Table(c).shape(3)
+    tab = R.Table(c).shape(R.entry_bytes("u8", 3))
     singles, batch = both(c, tab.K)
     assert batch == [tab.chunk_range(k) for k in R.plan_chunks(Wd, Ht, rects, tab.K, tab.N)]
     assert singles == [[tab.chunk_range(k) for k in R.plan_chunks(Wd, Ht, [r], tab.K, tab.N)] for r in rects]
     E5 = 6 + 3 * 5 + (12 * 5 * 12 + 7) // 8
     c = with_table(oracle.encode(oracle.generate(Wd, Ht, 5, U16, "LANDSAT16", 2), U16, FTL), E5, 12, Wd, Ht)
-    singles, batch = both(c, R16.Table(c).shape(E5).K)
+    singles, batch = both(c, R.Table(c).shape(E5).K)
     assert batch == [] and all(s == [] for s in singles)
     singles, batch = both(oracle.encode(oracle.generate(Wd, Ht, 4, U16, "LANDSAT16", 2), U16, FTL), 0)
     assert batch == [] and all(s == [] for s in singles)

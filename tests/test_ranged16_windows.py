@@ -2,7 +2,7 @@
 k_dec_wins16_ranged.hip).  The invariant is the window calls': every window is the crop of what the whole decode writes, nothing
 outside a window's rows is written.  Expected bytes are the crop of the SOURCE raster (lossless containers) or of
 qb3x_decode_device on a second handle (quanta), never of a window call.  What the reader is asked for is the range rule of qb3x.h
-with the raster's blocks per segment, restated in qb3_ranged16.py and computed from the container's own table -- and the whole
+with the raster's blocks per segment, restated in qb3_ranged.py and computed from the container's own table -- and the whole
 container, once, wherever the shortcut is not taken.  Containers are written by this library at level 2 and held in a numpy
 buffer behind a reader that logs its calls."""
 import ctypes as C
@@ -14,24 +14,22 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import qb3_ranged as R  # noqa: E402
-import qb3_ranged16 as R16  # noqa: E402
 import qb3_window as W  # noqa: E402
 import qb3_window16 as W16  # noqa: E402
-from test_window16_decode import Layout, SENTINEL, as_rows, full_decode, make_container  # noqa: E402
+from qb3_ranged import check_fallback, check_host, counters, device_call, host_call, host_container, open_source  # noqa: E402
+from qb3_window_dev import FTL, BASE, BASE_Z, CF_H, SENTINEL, Layout, as_rows, count, full_decode, make_container, paths  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-FTL, BASE, BASE_Z, CF_H = 8, 4, 0, 5
 U16, I16 = W16.U16, W16.I16
 BIT = W16.QB3X_WINK_U16
-_vp = C.c_void_p
 
 
 class Placed(Layout):
     """tight windows at chosen addresses: window k starts at a multiple of 16 plus mods[k] bytes"""
 
     def __init__(self, rects, pix, mods):
-        self.rects, self.pix, self.offs, self.sbytes = rects, pix, [], []
+        self.rects, self.pix, self.tsz, self.offs, self.sbytes = rects, pix, 2, [], []
         at = 16
         for (x0, y0, w, h), m in zip(rects, mods):
             at = (at + 15) // 16 * 16 + m
@@ -41,63 +39,10 @@ class Placed(Layout):
         self.size = at + 64
 
 
-def host_container(qb3, img, dt, mode, level=2, quanta=1):
-    d_c, n, _ = make_container(qb3, img, dt, mode, level, quanta=quanta)
-    return d_c[:n].cpu().numpy()
-
-
-def open_source(qb3, c, mask=BIT):
-    src = R.Source(qb3, c)
-    p, dims = src.open(qb3)
-    assert p
-    qb3.lib.qb3x_set_decoder_window_kernels(p, mask)
-    del src.log[:]
-    return src, p, dims
-
-
-def host_call(qb3, p, lay, hbuf, sel=None):
-    """qb3x_read_windows_ranged of the layout's windows (or of window `sel` alone) into the host buffer; returns the count"""
-    ks = range(len(lay.rects)) if sel is None else [sel]
-    rects = [lay.rects[k] for k in ks]
-    strides = [0 if lay.sbytes[k] == lay.rects[k][2] * lay.pix else lay.sbytes[k] // 2 for k in ks]
-    wins = qb3.window_array(rects, [hbuf.ctypes.data + lay.offs[k] for k in ks], strides)
-    return qb3.lib.qb3x_read_windows_ranged(p, wins, len(rects))
-
-
-def device_buffer(lay):
-    import torch
-    return torch.full((lay.size,), SENTINEL, dtype=torch.uint8, device="cuda")
-
-
-def device_call(qb3, p, lay, buf):
-    import torch
-    n = qb3.lib.qb3x_decode_windows_ranged(p, lay.array(qb3, buf), len(lay.rects), _vp(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    return n
-
-
-def check_host(lay, hbuf, rows):
-    import torch
-    lay.check(torch.from_numpy(hbuf).cuda(), rows)
-
-
-def paths(qb3, p, n):
-    return [qb3.lib.qb3x_window_path(p, i) for i in range(n)]
-
-
-def counters(qb3, p):
-    return qb3.lib.qb3x_ranged_bytes(p), qb3.lib.qb3x_ranged_reads(p)
-
-
 def segment_size(qb3, p, Wd, Ht):
     bps = C.c_size_t()
     qb3.lib.qb3x_window_segments(p, 0, 0, Wd, Ht, C.byref(bps))
     return bps.value
-
-
-def count(qb3, name):
-    ms, cnt = C.c_double(), C.c_uint64()
-    return cnt.value if qb3.lib.qb3x_profile_get(name.encode(), C.byref(ms), C.byref(cnt)) else 0
 
 
 # ---------------------------------------------------------------------------------------------------------------- parity
@@ -114,18 +59,18 @@ def test_windows_from_pieces(qb3, case):
     from qb3_amd import synth
     L = qb3.lib
     bands, (Wd, Ht) = case
-    pix, E, B = 2 * bands, R16.entry_bytes(bands), R16.blocks_per_segment(bands)
+    pix, E, B = 2 * bands, R.entry_bytes("u16", bands), R.blocks_per_segment("u16", bands)
     rects = W16.windows(Wd, Ht, 5 * Wd + bands, B, 16)
     for turn, mode in enumerate((FTL, BASE, BASE_Z)):
         dt = I16 if mode == BASE and bands in (1, 4, 8) else U16
         img = synth.generate(Wd, Ht, bands, dt, ("LANDSAT16", "DEM")[(turn + bands + Wd) % 2], 31 * bands + Wd)
         rows = as_rows(img, Ht)
         c = host_container(qb3, img, dt, mode)
-        tab = R16.Table(c).shape(E)
-        src, p, dims = open_source(qb3, c)
+        tab = R.Table(c).shape(E)
+        src, p, dims = open_source(qb3, c, BIT)
         assert dims == (Wd, Ht, bands) and L.qb3_get_mode(p) == mode and L.qb3x_decoder_table_entries(p) == tab.K
         assert segment_size(qb3, p, Wd, Ht) == B
-        lay = Layout(rects, pix)
+        lay = Layout(rects, pix, 2, "u16")
         # single calls
         hbuf = np.full(lay.size, SENTINEL, np.uint8)
         cached = set()
@@ -134,14 +79,14 @@ def test_windows_from_pieces(qb3, case):
             assert host_call(qb3, p, lay, hbuf, k) == 1, (r, qb3.last_error())
             assert L.qb3x_window_path(p, 0) == 1 and L.qb3x_last_window_path(p) == 1, r
             assert L.qb3x_last_window_segments(p) == W.brute_segments(Wd, Ht, *r, bps=B), r
-            want = R16.plan_bytes(Wd, Ht, [r], tab, B, 0, cached)
+            want = R.plan_bytes(Wd, Ht, [r], tab, 0, cached, B)
             assert counters(qb3, p) == want == (src.bytes_logged(), len(src.log)), r
-            cached.update(R16.plan_chunks(Wd, Ht, [r], tab.K, tab.N, B))
+            cached.update(R.plan_chunks(Wd, Ht, [r], tab.K, tab.N, B))
         check_host(lay, hbuf, rows)
         assert not src.outside
         # one batch, on a fresh handle (an empty cache), twice: the second reads no table chunk
         L.qb3_destroy_decoder(p)
-        src, p, _ = open_source(qb3, c)
+        src, p, _ = open_source(qb3, c, BIT)
         all_chunks = set(range(len(tab.chunks)))
         for again in (False, True):
             del src.log[:]
@@ -150,13 +95,13 @@ def test_windows_from_pieces(qb3, case):
             assert paths(qb3, p, len(rects)) == [1] * len(rects) and all(L.qb3x_window_ok(p, i) == 1 for i in range(len(rects)))
             assert L.qb3x_last_window_segments(p) == sum(W.brute_segments(Wd, Ht, *r, bps=B) for r in rects)
             assert np.array_equal(hbuf2, hbuf)
-            assert counters(qb3, p) == R16.plan_bytes(Wd, Ht, rects, tab, B, 0, all_chunks if again else ()) == (src.bytes_logged(), len(src.log))
+            assert counters(qb3, p) == R.plan_bytes(Wd, Ht, rects, tab, 0, all_chunks if again else (), B) == (src.bytes_logged(), len(src.log))
             if again:
                 ranges = [tab.chunk_range(k) for k in range(len(tab.chunks))]
                 assert all(off >= tab.D // 4 * 4 and (off, n) not in ranges for off, n in src.log)
         # gaps: fewer reads, at least as many bytes, the same pixels
         some = rects[5:] if Wd * Ht < 200000 else [r for r in rects if r[2] < Wd // 2][:8]
-        sub = Layout(some, pix)
+        sub = Layout(some, pix, 2, "u16")
         got = {}
         for gap in (0, 64, 1 << 20):
             L.qb3x_set_ranged_gap(p, gap)
@@ -165,25 +110,25 @@ def test_windows_from_pieces(qb3, case):
             assert host_call(qb3, p, sub, hb) == len(some)
             check_host(sub, hb, rows)
             got[gap] = counters(qb3, p)
-            assert got[gap] == R16.plan_bytes(Wd, Ht, some, tab, B, gap, all_chunks) == (src.bytes_logged(), len(src.log)), gap
+            assert got[gap] == R.plan_bytes(Wd, Ht, some, tab, gap, all_chunks, B) == (src.bytes_logged(), len(src.log)), gap
         assert got[0][1] >= got[64][1] >= got[1 << 20][1] >= 1 and got[0][0] <= got[64][0] <= got[1 << 20][0]
-        if len(R16.plan_pieces(Wd, Ht, some, tab, B, 0)) > 1:
+        if len(R.plan_pieces(Wd, Ht, some, tab, 0, B)) > 1:
             assert got[1 << 20][1] < got[0][1]
         L.qb3x_set_ranged_gap(p, 0)
         # device destinations: window k starts k % 8 halfwords behind a dword; rows tight, wide-even, wide-odd
         del src.log[:]
-        dbuf = device_buffer(lay)
+        dbuf = lay.buffer()
         assert {(dbuf.data_ptr() + o) % 4 for o in lay.offs} == {0, 2}
         assert device_call(qb3, p, lay, dbuf) == len(rects), qb3.last_error()
         assert paths(qb3, p, len(rects)) == [1] * len(rects)
         lay.check(dbuf, rows)
         assert np.array_equal(dbuf.cpu().numpy(), hbuf)
-        assert counters(qb3, p) == R16.plan_bytes(Wd, Ht, rects, tab, B, 0, all_chunks) == (src.bytes_logged(), len(src.log))
+        assert counters(qb3, p) == R.plan_bytes(Wd, Ht, rects, tab, 0, all_chunks, B) == (src.bytes_logged(), len(src.log))
         if bands == 8:          # whole blocks of tight windows whose rows lie on a 16-byte address, 8 behind one, 4 and 2 behind one
             inner = [r for r in rects if r[2] >= 12 and r[3] >= 4][:8]
             mods = [(0, 8, 4, 2)[k % 4] for k in range(len(inner))]
             pl = Placed(inner, pix, mods)
-            dbuf = device_buffer(pl)
+            dbuf = pl.buffer()
             assert len(inner) >= 4 and sorted({(dbuf.data_ptr() + o) % 16 for o in pl.offs}) == [0, 2, 4, 8] and all(sb % 16 == 0 for sb in pl.sbytes)
             assert device_call(qb3, p, pl, dbuf) == len(inner) and paths(qb3, p, len(inner)) == [1] * len(inner)
             pl.check(dbuf, rows)
@@ -199,10 +144,10 @@ def test_one_launch_of_the_kernel_that_applies(qb3):
     try:
         for bands, dt, gen, pix, want in ((4, U16, "LANDSAT16", 8, (1, 0)), (3, 0, "NOISY3", 3, (0, 1))):
             img = synth.generate(260, 37, bands, dt, gen, 1)
-            src, p, _ = open_source(qb3, host_container(qb3, img, dt, FTL))
+            src, p, _ = open_source(qb3, host_container(qb3, img, dt, FTL), BIT)
             rects = W16.windows(260, 37, 4, 64, 8)
-            lay = Layout(rects, pix) if dt else __import__("test_window_batch").Layout(rects, pix, 1)
-            buf = device_buffer(lay)
+            lay = Layout(rects, pix, 2, "u16") if dt else Layout(rects, pix, 1, "u8")
+            buf = lay.buffer()
             L.qb3x_profile_reset()
             assert device_call(qb3, p, lay, buf) == len(rects) and paths(qb3, p, len(rects)) == [1] * len(rects)
             lay.check(buf, as_rows(img, 37))
@@ -220,16 +165,16 @@ def test_quanta(qb3):
     Wd, Ht, b = 260, 37, 4
     img = synth.generate(Wd, Ht, b, U16, "LANDSAT16", 11)
     d_c, n, _ = make_container(qb3, img, U16, BASE, 2, quanta=3)
-    want = full_decode(qb3, d_c, n)
+    want = full_decode(qb3, d_c, n)[0]
     assert want is not None and not torch.equal(want, img.reshape(-1).view(torch.uint8))
-    src, p, _ = open_source(qb3, d_c[:n].cpu().numpy())
+    src, p, _ = open_source(qb3, d_c[:n].cpu().numpy(), BIT)
     rects = W16.windows(Wd, Ht, 3, 64, 8)
-    lay = Layout(rects, 2 * b)
+    lay = Layout(rects, 2 * b, 2, "u16")
     hbuf = np.full(lay.size, SENTINEL, np.uint8)
     assert host_call(qb3, p, lay, hbuf) == len(rects)
     check_host(lay, hbuf, want.view(Ht, -1))
     assert paths(qb3, p, len(rects)) == [1] * len(rects)
-    dbuf = device_buffer(lay)
+    dbuf = lay.buffer()
     assert device_call(qb3, p, lay, dbuf) == len(rects) and paths(qb3, p, len(rects)) == [1] * len(rects)
     lay.check(dbuf, want.view(Ht, -1))
     qb3.lib.qb3_destroy_decoder(p)
@@ -265,28 +210,6 @@ def test_python_interface(qb3, tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------------------- falling back
-def check_fallback(qb3, c, rows, lay, want_paths, mask=BIT, host=True):
-    """host (unless host is False) and device destinations: all windows written and exact, on the paths named, and the whole
-    container read, once a call"""
-    L = qb3.lib
-    n = len(lay.rects)
-    src, p, _ = open_source(qb3, c, mask)
-    for dev in (False, True) if host else (True,):
-        del src.log[:]
-        if dev:
-            buf = device_buffer(lay)
-            assert device_call(qb3, p, lay, buf) == n, qb3.last_error()
-            lay.check(buf, rows)
-        else:
-            hbuf = np.full(lay.size, SENTINEL, np.uint8)
-            assert host_call(qb3, p, lay, hbuf) == n, qb3.last_error()
-            check_host(lay, hbuf, rows)
-        assert set(paths(qb3, p, n)) <= set(want_paths), paths(qb3, p, n)
-        assert L.qb3x_ranged_bytes(p) >= len(c)
-        assert src.log.count((0, len(c))) == 1 and not src.outside
-    L.qb3_destroy_decoder(p)
-
-
 def test_not_taken(qb3):
     """the bit unset on uint16 x 4; the bit set with one odd device destination in the batch; uint16 x 5; uint16 x 4 in QB3M_CF_H; a
     level-1 table: the whole container read once, the right pixels, the path reported today"""
@@ -296,14 +219,14 @@ def test_not_taken(qb3):
     img = synth.generate(Wd, Ht, 4, U16, "LANDSAT16", 3)
     rows = as_rows(img, Ht)
     c = host_container(qb3, img, U16, FTL)
-    check_fallback(qb3, c, rows, Layout(rects, 8), (2,), mask=0)
-    odd = Layout(rects, 8)
+    check_fallback(qb3, c, rows, Layout(rects, 8, 2, "u16"), (2,), mask=0)
+    odd = Layout(rects, 8, 2, "u16")
     odd.offs[3] += 1                                   # (six sentinel bytes lie between two windows)
-    check_fallback(qb3, c, rows, odd, (2,), host=False)
+    check_fallback(qb3, c, rows, odd, (2,), BIT, host=False)
     img5 = synth.generate(Wd, Ht, 5, U16, "LANDSAT16", 3)
-    check_fallback(qb3, host_container(qb3, img5, U16, FTL), as_rows(img5, Ht), Layout(rects, 10), (2,))
-    check_fallback(qb3, host_container(qb3, img, U16, CF_H), rows, Layout(rects, 8), (2,))
-    check_fallback(qb3, host_container(qb3, img, U16, FTL, level=1), rows, Layout(rects, 8), (3,))
+    check_fallback(qb3, host_container(qb3, img5, U16, FTL), as_rows(img5, Ht), Layout(rects, 10, 2, "u16"), (2,), BIT)
+    check_fallback(qb3, host_container(qb3, img, U16, CF_H), rows, Layout(rects, 8, 2, "u16"), (2,), BIT)
+    check_fallback(qb3, host_container(qb3, img, U16, FTL, level=1), rows, Layout(rects, 8, 2, "u16"), (3,), BIT)
 
 
 @pytest.mark.parametrize("bands", (4, 8))
@@ -314,11 +237,11 @@ def test_damaged_tables_cost_time_and_bytes(qb3, bands):
     from qb3_amd import synth
     L = qb3.lib
     Wd, Ht = 1001, 259
-    pix, E, B = 2 * bands, R16.entry_bytes(bands), R16.blocks_per_segment(bands)
+    pix, E, B = 2 * bands, R.entry_bytes("u16", bands), R.blocks_per_segment("u16", bands)
     img = synth.generate(Wd, Ht, bands, U16, "DEM", 5)
     rows = as_rows(img, Ht)
     c = host_container(qb3, img, U16, FTL)
-    tab = R16.Table(c).shape(E)
+    tab = R.Table(c).shape(E)
     nbx = (Wd + 3) // 4
     seg = (6 * nbx + 10) // B + 1                       # block row 6: its first block is column 30 for both segment sizes
     assert seg * B == 6 * nbx + 30
@@ -328,11 +251,11 @@ def test_damaged_tables_cost_time_and_bytes(qb3, bands):
         bx0, bx1, by0, by1, _ = R.block_rect(Wd, Ht, r)
         assert not {seg - 1, seg} & {(by * nbx + bx) // B for by in range(by0, by1 + 1) for bx in range(bx0, bx1 + 1)}
     e0 = tab.entry_offset(seg)
-    lay = Layout(holds + beside, pix)
+    lay = Layout(holds + beside, pix, 2, "u16")
     for at in (e0 + 7, e0 + 6 + 3 * bands + 11, tab.chunks[0][0] + 6, tab.chunks[-1][0] + tab.chunks[-1][1] - 1):
         bad = c.copy()
         bad[at] ^= 0x10
-        check_fallback(qb3, bad, rows, lay, (3,))
+        check_fallback(qb3, bad, rows, lay, (3,), BIT)
     damaged = []
     for moved in (tab.pos(seg) + 40, tab.pos(seg + 2), tab.pos(seg - 3), tab.pos(seg + 1) + 8 * 4096, (1 << 48) - 1):
         bad = c.copy()
@@ -347,8 +270,8 @@ def test_damaged_tables_cost_time_and_bytes(qb3, bands):
     damaged.append(("lane length", bad))
     for what, bad in damaged:
         R.seal(bad, tab.chunks[seg // tab.N][0])
-        src, p, _ = open_source(qb3, bad)
-        buf = device_buffer(lay)
+        src, p, _ = open_source(qb3, bad, BIT)
+        buf = lay.buffer()
         assert device_call(qb3, p, lay, buf) == len(lay.rects), what
         lay.check(buf, rows)
         assert paths(qb3, p, len(lay.rects)) == [3] * len(holds) + [1] * len(beside), what
@@ -374,12 +297,12 @@ def test_truncated_stream(qb3, bands):
     L = qb3.lib
     Wd, Ht = W16.SHAPES_NARROW[1]
     assert Wd % 4 == 0 and Ht % 4 == 0
-    pix, E, B = 2 * bands, R16.entry_bytes(bands), R16.blocks_per_segment(bands)
+    pix, E, B = 2 * bands, R.entry_bytes("u16", bands), R.blocks_per_segment("u16", bands)
     img = synth.generate(Wd, Ht, bands, U16, "LANDSAT16", 4)
     c = host_container(qb3, img, U16, BASE)
-    tab = R16.Table(c).shape(E)
+    tab = R.Table(c).shape(E)
     rects = W16.windows(Wd, Ht, 6, B, 8)
-    lay = Layout(rects, pix)
+    lay = Layout(rects, pix, 2, "u16")
     strides = [0 if sb == r[2] * pix else sb // 2 for sb, r in zip(lay.sbytes, rects)]
     for cut in (tab.D + tab.pos(tab.K - 1) // 8 + 30, tab.D + tab.pos(tab.K - 2) // 8 - 5, len(c) - 3):
         short = c[:cut].copy()
@@ -389,7 +312,7 @@ def test_truncated_stream(qb3, bands):
         n_ref = L.qb3x_read_windows(ref, qb3.window_array(rects, [want.ctypes.data + o for o in lay.offs], strides), len(rects))
         ref_paths = [L.qb3x_window_path(ref, i) for i in range(len(rects))]
         L.qb3_destroy_decoder(ref)
-        src, p, _ = open_source(qb3, short)
+        src, p, _ = open_source(qb3, short, BIT)
         hbuf = np.full(lay.size, SENTINEL, np.uint8)
         assert host_call(qb3, p, lay, hbuf) == n_ref, cut
         assert [bool(v) for v in paths(qb3, p, len(rects))] == [bool(v) for v in ref_paths]
@@ -410,13 +333,13 @@ def test_a_small_window_reads_a_small_part(qb3):
     img = synth.generate(Wd, Ht, b, U16, "LANDSAT16", 9)
     c = host_container(qb3, img, U16, FTL)
     assert len(c) >= 7 << 20
-    tab = R16.Table(c).shape(R16.entry_bytes(b))
+    tab = R.Table(c).shape(R.entry_bytes("u16", b))
     r = ((Wd - 64) // 2, (Ht - 64) // 2, 64, 64)
-    assert W.brute_segments(Wd, Ht, *r) <= 17 * 2 and len(R16.plan_chunks(Wd, Ht, [r], tab.K, tab.N, 64)) <= 3
-    want = R16.plan_bytes(Wd, Ht, [r], tab, 64)
+    assert W.brute_segments(Wd, Ht, *r) <= 17 * 2 and len(R.plan_chunks(Wd, Ht, [r], tab.K, tab.N, 64)) <= 3
+    want = R.plan_bytes(Wd, Ht, [r], tab, B=64)
     assert want[0] < len(c) // 10
-    src, p, _ = open_source(qb3, c)
-    lay = Layout([r], 2 * b)
+    src, p, _ = open_source(qb3, c, BIT)
+    lay = Layout([r], 2 * b, 2, "u16")
     hbuf = np.full(lay.size, SENTINEL, np.uint8)
     assert host_call(qb3, p, lay, hbuf) == 1 and L.qb3x_last_window_path(p) == 1
     check_host(lay, hbuf, as_rows(img, Ht))

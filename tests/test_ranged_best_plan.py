@@ -12,9 +12,9 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import qb3_ranged as R  # noqa: E402
-import qb3_ranged_best as RB  # noqa: E402
 import qb3_window16 as W16  # noqa: E402
 import qb3_window_best as WB  # noqa: E402
+from qb3_window_dev import chunk_check  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FTL = 8
@@ -24,12 +24,12 @@ SHAPES = WB.SHAPES + ((1280, 512),)
 RASTERS = ("FEW", "TERRACE", "NOISY3")     # test_window_best_plan.py: coded common-factor containers at every shape, band count, mode
 
 
-def with_table(c, E, blocks, W_, H_, version=3, flags=RB.HEAD_FLAGS):
+def with_table(c, E, blocks, W_, H_, version=3, flags=R.HEAD_FLAGS):
     """the container with a table in front of "DT": an entry of E bytes per `blocks` blocks, chunks of at most 65535 bytes with a pad
     behind each, positions that grow by 1000 bits, checks sealed"""
     c = np.asarray(c, np.uint8)
     K = (((W_ + 3) // 4) * ((H_ + 3) // 4) + blocks - 1) // blocks
-    N = (RB.CHUNK_MAX - R.IX_HEAD) // E
+    N = (R.CHUNK_MAX - R.IX_HEAD) // E
     at = R.Table(c).dt
     run = bytearray()
     for k0 in range(0, K, N):
@@ -39,7 +39,7 @@ def with_table(c, E, blocks, W_, H_, version=3, flags=RB.HEAD_FLAGS):
         for j in range(here):
             body[j * E:j * E + 6] = (1000 * (k0 + j)).to_bytes(6, "little")
             body[j * E + 6:j * E + E] = bytes((7 * (k0 + j) + i) & 0xff for i in range(E - 6))
-        chk = R.chunk_check(body)
+        chk = chunk_check(body)
         run += b"ix" + bytes([ln & 255, ln >> 8, version, flags, chk & 255, chk >> 8]) + blocks.to_bytes(4, "little") + body + b"zz\x04\x00"
     return np.concatenate([c[:at], np.frombuffer(bytes(run), np.uint8), c[at:]])
 
@@ -65,20 +65,20 @@ def windows_of(Wd, Ht, seed):
 def test_table_ranges_follow_the_rule_with_the_bit(qb3, oracle, shape, bands):
     """QB3M_CF, QB3M_CF_H and QB3M_BEST containers (mode byte 1 or 5, asserted) with a table of head flags 3, version 3, 64 blocks
     and entries of 6 + 3 * bands + 192 bytes.  Without the bit, and with QB3X_WINK_U16 alone: nothing is planned (the file is read
-    whole).  With QB3X_WINK_CF8: the chunk ranges of the rule restated in qb3_ranged_best.py, for single rectangles and for batches
+    whole).  With QB3X_WINK_CF8: the chunk ranges of the rule restated in qb3_ranged.py, for single rectangles and for batches
     that share chunks; a bad rectangle plans nothing; the reader is never called"""
     L = qb3.lib
     Wd, Ht = shape
-    E = RB.entry_bytes(bands)
+    E = R.entry_bytes("cf8", bands)
     assert E == 6 + 3 * bands + 192
     for turn, mode in enumerate(WB.MODES):
         name = RASTERS[(turn + bands + Wd) % 3]
         plain = oracle.encode(WB.raster(oracle.generate, name, Wd, Ht, bands, 7 * Wd + bands), 0, mode)
         assert int(plain[10]) == (1 if mode == WB.CF else 5), (name, mode)         # a coded common-factor container, or the case tests nothing
-        c = with_table(plain, E, RB.B, Wd, Ht)
-        tab = RB.Table(c).shape(bands)
+        c = with_table(plain, E, R.blocks_per_segment("cf8", bands), Wd, Ht)
+        tab = R.Table(c).shape(E, R.HEAD_FLAGS)
         nseg = (((Wd + 3) // 4) * ((Ht + 3) // 4) + 63) // 64
-        assert tab.K == nseg and tab.N == min(RB.per_chunk(bands), nseg) and len(tab.chunks) == (nseg + tab.N - 1) // tab.N
+        assert tab.K == nseg and tab.N == min((R.CHUNK_MAX - R.IX_HEAD) // E, nseg) and len(tab.chunks) == (nseg + tab.N - 1) // tab.N
         if shape == (1280, 512):        # the chunk count from E and IX_HEAD: 640 entries at 316 (3 bands), 312 (4) or 325 (1) a chunk
             assert nseg == 640 and len(tab.chunks) == -(-640 // ((65535 - R.IX_HEAD) // E)) == (2 if bands == 1 else 3)
         src = R.Source(qb3, c)
@@ -93,17 +93,17 @@ def test_table_ranges_follow_the_rule_with_the_bit(qb3, oracle, shape, bands):
             L.qb3x_set_decoder_window_kernels(p, mask)
             seen = set()
             for r in rects:
-                want = [tab.chunk_range(k) for k in RB.plan_chunks(Wd, Ht, [r], tab.K, tab.N)]
+                want = [tab.chunk_range(k) for k in R.plan_chunks(Wd, Ht, [r], tab.K, tab.N)]
                 assert want and table_ranges(qb3, p, [r]) == want, (mode, r)
                 seen.add(len(want))
             assert seen >= set(range(1, len(tab.chunks) + 1)) or len(tab.chunks) == 1
             for batch in (rects, rects[1:5], rects[5:], rects[::3]):
-                assert table_ranges(qb3, p, batch) == [tab.chunk_range(k) for k in RB.plan_chunks(Wd, Ht, batch, tab.K, tab.N)]
+                assert table_ranges(qb3, p, batch) == [tab.chunk_range(k) for k in R.plan_chunks(Wd, Ht, batch, tab.K, tab.N)]
         last = len(tab.chunks) - 1
         assert tab.chunk_range(last)[0] + tab.chunk_range(last)[1] == tab.D
         wins = qb3.window_array(rects, [0] * len(rects))
         one = (qb3.Range * 1)()
-        assert L.qb3x_ranged_table_ranges(p, wins, len(rects), one, 1) == len(RB.plan_chunks(Wd, Ht, rects, tab.K, tab.N))
+        assert L.qb3x_ranged_table_ranges(p, wins, len(rects), one, 1) == len(R.plan_chunks(Wd, Ht, rects, tab.K, tab.N))
         assert (int(one[0].offset), int(one[0].size)) == tab.chunk_range(0)
         assert table_ranges(qb3, p, [(0, 0, Wd + 1, 1)]) == [] and table_ranges(qb3, p, [(0, 0, 0, 1)]) == []
         assert table_ranges(qb3, p, [rects[0], (0, 0, Wd + 1, 1)]) == []
@@ -134,7 +134,7 @@ def test_the_bit_changes_nothing_for_an_ftl_container(qb3, oracle):
     Wd, Ht = 1001, 259
     rects = W16.windows(Wd, Ht, 11, 64)
     c = with_table(oracle.encode(oracle.generate(Wd, Ht, 3, 0, "NOISY3", 2), 0, FTL), 6 + 2 * 3 + 80, 64, Wd, Ht, flags=2)
-    tab = R.Table(c).shape(3)
+    tab = R.Table(c).shape(R.entry_bytes("u8", 3))
     without, with_bit = plans(qb3, c, rects, tab.K)
     assert without == with_bit
     assert with_bit[1] == [tab.chunk_range(k) for k in R.plan_chunks(Wd, Ht, rects, tab.K, tab.N)]
@@ -199,10 +199,10 @@ def test_the_bit_plans_nothing_without_a_usable_table(qb3, oracle):
     for singles, batch in plans(qb3, c, rects, K):
         assert batch == [] and all(s == [] for s in singles)
     # ... while the same container with the table of its own kind is planned (the control of the two cases above)
-    c = with_table(plain, RB.entry_bytes(3), 64, Wd, Ht)
-    tab = RB.Table(c).shape(3)
+    c = with_table(plain, R.entry_bytes("cf8", 3), 64, Wd, Ht)
+    tab = R.Table(c).shape(R.entry_bytes("cf8", 3), R.HEAD_FLAGS)
     without, with_bit = plans(qb3, c, rects, tab.K)
-    assert without[1] == [] and with_bit[1] == [tab.chunk_range(k) for k in RB.plan_chunks(Wd, Ht, rects, tab.K, tab.N)]
+    assert without[1] == [] and with_bit[1] == [tab.chunk_range(k) for k in R.plan_chunks(Wd, Ht, rects, tab.K, tab.N)]
 
 
 def test_header_text(qb3):

@@ -2,10 +2,9 @@
 k_dec_wins_best_ranged.hip).  The invariant is the window calls': every window is the crop of what the whole decode writes, nothing
 outside a window's rows is written.  Expected bytes are the crop of the SOURCE raster (lossless containers) or of qb3x_decode_device
 on a second handle (quanta), never of a window call.  What the reader is asked for is the range rule of qb3x.h, restated in
-qb3_ranged_best.py and computed from the container's own table -- and the whole container, once, wherever the shortcut is not taken.
+qb3_ranged.py and computed from the container's own table -- and the whole container, once, wherever the shortcut is not taken.
 Containers are written by this library and held in a numpy buffer behind a reader that logs its calls.  Every damaged input is table
 or stream bytes the kernel bounds by the piece it was given: no case depends on an access outside the uploaded arrays."""
-import ctypes as C
 import os
 import sys
 
@@ -14,66 +13,18 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import qb3_ranged as R  # noqa: E402
-import qb3_ranged_best as RB  # noqa: E402
 import qb3_window as W  # noqa: E402
 import qb3_window16 as W16  # noqa: E402
 import qb3_window_best as WB  # noqa: E402
-from test_window_best_decode import Layout, SENTINEL, as_rows, count, device_raster, full_decode, make_container, segments_of  # noqa: E402
+from qb3_ranged import check_fallback, check_host, counters, device_call, host_call, host_container, open_source  # noqa: E402
+from qb3_window_best import device_raster  # noqa: E402
+from qb3_window_dev import SENTINEL, Layout, as_rows, count, full_decode, make_container, paths, segments_of  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 CF, CF_H, BEST = WB.CF, WB.CF_H, WB.BEST
 BIT = WB.QB3X_WINK_CF8
 SMALLEST = (256, 24)
-_vp = C.c_void_p
-
-
-def host_container(qb3, img, mode, level=2, cband=None, quanta=1):
-    d_c, n, _ = make_container(qb3, img, 0, mode, level, cband, quanta=quanta)
-    return d_c[:n].cpu().numpy()
-
-
-def open_source(qb3, c, mask=BIT):
-    src = R.Source(qb3, c)
-    p, dims = src.open(qb3)
-    assert p
-    qb3.lib.qb3x_set_decoder_window_kernels(p, mask)
-    del src.log[:]
-    return src, p, dims
-
-
-def host_call(qb3, p, lay, hbuf, sel=None):
-    """qb3x_read_windows_ranged of the layout's windows (or of window `sel` alone) into the host buffer; returns the count"""
-    ks = range(len(lay.rects)) if sel is None else [sel]
-    strides = lay.strides()
-    wins = qb3.window_array([lay.rects[k] for k in ks], [hbuf.ctypes.data + lay.offs[k] for k in ks], [strides[k] for k in ks])
-    return qb3.lib.qb3x_read_windows_ranged(p, wins, len(ks))
-
-
-def device_buffer(lay):
-    import torch
-    return torch.full((lay.size,), SENTINEL, dtype=torch.uint8, device="cuda")
-
-
-def device_call(qb3, p, lay, buf):
-    import torch
-    wins = qb3.window_array(lay.rects, [buf.data_ptr() + o for o in lay.offs], lay.strides())
-    n = qb3.lib.qb3x_decode_windows_ranged(p, wins, len(lay.rects), _vp(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    return n
-
-
-def check_host(lay, hbuf, rows):
-    import torch
-    lay.check(torch.from_numpy(hbuf).cuda(), rows)
-
-
-def paths(qb3, p, n):
-    return [qb3.lib.qb3x_window_path(p, i) for i in range(n)]
-
-
-def counters(qb3, p):
-    return qb3.lib.qb3x_ranged_bytes(p), qb3.lib.qb3x_ranged_reads(p)
 
 
 # ---------------------------------------------------------------------------------------------------------------- parity
@@ -100,12 +51,12 @@ def test_windows_from_pieces(qb3, oracle, shape, bands):
         what = (name, mode, level, cband)
         img = device_raster(oracle, name, Wd, Ht, bands, 7 * Wd + bands)
         rows = as_rows(img, Ht)
-        c = host_container(qb3, img, mode, level, cband)
+        c = host_container(qb3, img, 0, mode, level, cband)
         assert int(c[10]) == (1 if mode == CF else 5), what
-        tab = RB.Table(c).shape(bands)
+        tab = R.Table(c).shape(R.entry_bytes("cf8", bands), R.HEAD_FLAGS)
         rects = W16.windows(Wd, Ht, 5 * Wd + bands + turn, 64, 4 if full else 10)
-        lay = Layout(rects, bands)
-        src, p, dims = open_source(qb3, c)
+        lay = Layout(rects, bands, 1, "cf8")
+        src, p, dims = open_source(qb3, c, BIT)
         assert dims == (Wd, Ht, bands) and L.qb3x_decoder_table_entries(p) == tab.K, what
         # single calls (on the smallest shape for every third container: its full cross is about the containers)
         hbuf = None
@@ -117,14 +68,14 @@ def test_windows_from_pieces(qb3, oracle, shape, bands):
                 assert host_call(qb3, p, lay, hbuf, k) == 1, (what, r, qb3.last_error())
                 assert L.qb3x_window_path(p, 0) == 1 and L.qb3x_last_window_path(p) == 1, (what, r)
                 assert L.qb3x_last_window_segments(p) == W.brute_segments(Wd, Ht, *r), (what, r)
-                want = RB.plan_bytes(Wd, Ht, [r], tab, 0, cached)
+                want = R.plan_bytes(Wd, Ht, [r], tab, 0, cached)
                 assert counters(qb3, p) == want == (src.bytes_logged(), len(src.log)), (what, r)
-                cached.update(RB.plan_chunks(Wd, Ht, [r], tab.K, tab.N))
+                cached.update(R.plan_chunks(Wd, Ht, [r], tab.K, tab.N))
             check_host(lay, hbuf, rows)
             assert not src.outside
         # one batch, on a fresh handle (an empty cache), twice: the second reads no table chunk
         L.qb3_destroy_decoder(p)
-        src, p, _ = open_source(qb3, c)
+        src, p, _ = open_source(qb3, c, BIT)
         all_chunks = set(range(len(tab.chunks)))
         for again in (False, True):
             del src.log[:]
@@ -136,13 +87,13 @@ def test_windows_from_pieces(qb3, oracle, shape, bands):
                 check_host(lay, hbuf2, rows)
                 hbuf = hbuf2
             assert np.array_equal(hbuf2, hbuf), what
-            assert counters(qb3, p) == RB.plan_bytes(Wd, Ht, rects, tab, 0, all_chunks if again else ()) == (src.bytes_logged(), len(src.log)), what
+            assert counters(qb3, p) == R.plan_bytes(Wd, Ht, rects, tab, 0, all_chunks if again else ()) == (src.bytes_logged(), len(src.log)), what
             if again:
                 ranges = [tab.chunk_range(k) for k in range(len(tab.chunks))]
                 assert all(off >= tab.D // 4 * 4 and (off, n) not in ranges for off, n in src.log)
         # gaps: fewer reads, at least as many bytes, the same pixels
         some = rects[5:] if Wd * Ht < 200000 else [r for r in rects if r[2] < Wd // 2][:8]
-        sub = Layout(some, bands)
+        sub = Layout(some, bands, 1, "cf8")
         got = {}
         for gap in (0, 64, 1 << 20):
             L.qb3x_set_ranged_gap(p, gap)
@@ -151,14 +102,14 @@ def test_windows_from_pieces(qb3, oracle, shape, bands):
             assert host_call(qb3, p, sub, hb) == len(some), what
             check_host(sub, hb, rows)
             got[gap] = counters(qb3, p)
-            assert got[gap] == RB.plan_bytes(Wd, Ht, some, tab, gap, all_chunks) == (src.bytes_logged(), len(src.log)), (what, gap)
+            assert got[gap] == R.plan_bytes(Wd, Ht, some, tab, gap, all_chunks) == (src.bytes_logged(), len(src.log)), (what, gap)
         assert got[0][1] >= got[64][1] >= got[1 << 20][1] >= 1 and got[0][0] <= got[64][0] <= got[1 << 20][0]
-        if len(RB.plan_pieces(Wd, Ht, some, tab, 0)) > 1:
+        if len(R.plan_pieces(Wd, Ht, some, tab, 0)) > 1:
             assert got[1 << 20][1] < got[0][1]
         L.qb3x_set_ranged_gap(p, 0)
         # device destinations: window k starts k % 4 bytes behind a dword; rows tight, a few bytes wider, whole dwords wider
         del src.log[:]
-        dbuf = device_buffer(lay)
+        dbuf = lay.buffer()
         assert {(dbuf.data_ptr() + o) % 4 for o in lay.offs} == {0, 1, 2, 3}
         extra = [sb - r[2] * bands for sb, r in zip(lay.sbytes, rects)]
         assert 0 in extra and any(e % 4 for e in extra) and any(e and e % 4 == 0 for e in extra)
@@ -166,7 +117,7 @@ def test_windows_from_pieces(qb3, oracle, shape, bands):
         assert paths(qb3, p, len(rects)) == [1] * len(rects), what
         lay.check(dbuf, rows)
         assert np.array_equal(dbuf.cpu().numpy(), hbuf), what
-        assert counters(qb3, p) == RB.plan_bytes(Wd, Ht, rects, tab, 0, all_chunks) == (src.bytes_logged(), len(src.log)), what
+        assert counters(qb3, p) == R.plan_bytes(Wd, Ht, rects, tab, 0, all_chunks) == (src.bytes_logged(), len(src.log)), what
         assert not src.outside
         L.qb3_destroy_decoder(p)
 
@@ -182,10 +133,10 @@ def test_one_launch_of_the_kernel_that_applies(qb3, oracle):
     try:
         for bands, mode, level, want in ((3, BEST, 2, (1, 0)), (4, CF_H, 1, (1, 0)), (1, CF, 2, (1, 0)), (3, 8, 2, (0, 1))):
             img = device_raster(oracle, "mixed", Wd, Ht, bands, 1) if mode != 8 else synth.generate(Wd, Ht, bands, 0, "NOISY3", 1)
-            src, p, _ = open_source(qb3, host_container(qb3, img, mode, level))
+            src, p, _ = open_source(qb3, host_container(qb3, img, 0, mode, level), BIT)
             rects = W16.windows(Wd, Ht, 4, 64, 8)
-            lay = Layout(rects, bands)
-            buf = device_buffer(lay)
+            lay = Layout(rects, bands, 1, "cf8")
+            buf = lay.buffer()
             L.qb3x_profile_reset()
             assert device_call(qb3, p, lay, buf) == len(rects) and paths(qb3, p, len(rects)) == [1] * len(rects)
             lay.check(buf, as_rows(img, Ht))
@@ -203,17 +154,17 @@ def test_quanta(qb3, oracle):
     Wd, Ht, b = 260, 37, 3
     img = device_raster(oracle, "mixed", Wd, Ht, b, 11)
     d_c, n, _ = make_container(qb3, img, 0, CF_H, 2, quanta=3)
-    want = full_decode(qb3, d_c, n)
+    want = full_decode(qb3, d_c, n)[0]
     assert want is not None and not torch.equal(want, img.reshape(-1))
-    src, p, _ = open_source(qb3, d_c[:n].cpu().numpy())
+    src, p, _ = open_source(qb3, d_c[:n].cpu().numpy(), BIT)
     assert qb3.lib.qb3_get_mode(p) == 5
     rects = W16.windows(Wd, Ht, 3, 64, 8)
-    lay = Layout(rects, b)
+    lay = Layout(rects, b, 1, "cf8")
     hbuf = np.full(lay.size, SENTINEL, np.uint8)
     assert host_call(qb3, p, lay, hbuf) == len(rects)
     check_host(lay, hbuf, want.view(Ht, -1))
     assert paths(qb3, p, len(rects)) == [1] * len(rects)
-    dbuf = device_buffer(lay)
+    dbuf = lay.buffer()
     assert device_call(qb3, p, lay, dbuf) == len(rects) and paths(qb3, p, len(rects)) == [1] * len(rects)
     lay.check(dbuf, want.view(Ht, -1))
     qb3.lib.qb3_destroy_decoder(p)
@@ -224,7 +175,7 @@ def test_python_interface(qb3, oracle, tmp_path):
     from qb3_amd import device as qdev
     Wd, Ht, b = 260, 100, 4
     img = device_raster(oracle, "mixed", Wd, Ht, b, 8)
-    c = host_container(qb3, img, BEST)
+    c = host_container(qb3, img, 0, BEST)
     assert int(c[10]) == 5
     path = tmp_path / "a.qb3"
     c.tofile(path)
@@ -250,27 +201,6 @@ def test_python_interface(qb3, oracle, tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------------------- falling back
-def check_fallback(qb3, c, rows, lay, want_paths, mask=BIT):
-    """host and device destinations: all windows written and exact, on the paths named, and the whole container read, once a call"""
-    L = qb3.lib
-    n = len(lay.rects)
-    src, p, _ = open_source(qb3, c, mask)
-    for dev in (False, True):
-        del src.log[:]
-        if dev:
-            buf = device_buffer(lay)
-            assert device_call(qb3, p, lay, buf) == n, qb3.last_error()
-            lay.check(buf, rows)
-        else:
-            hbuf = np.full(lay.size, SENTINEL, np.uint8)
-            assert host_call(qb3, p, lay, hbuf) == n, qb3.last_error()
-            check_host(lay, hbuf, rows)
-        assert set(paths(qb3, p, n)) <= set(want_paths), paths(qb3, p, n)
-        assert L.qb3x_ranged_bytes(p) >= len(c)
-        assert src.log.count((0, len(c))) == 1 and not src.outside
-    L.qb3_destroy_decoder(p)
-
-
 def test_not_taken(qb3, oracle):
     """the bit unset on an RGB QB3M_CF_H container, and QB3X_WINK_U16 alone (path 2: strips of the whole container); the bit set on
     8-bit x 2 in QB3M_CF_H (path 2) and on a QB3M_BEST container whose RLE0 pass won (all zeros: the mode byte says 7; path 3): the
@@ -281,19 +211,19 @@ def test_not_taken(qb3, oracle):
     Wd, Ht = 260, 37
     rects = W16.windows(Wd, Ht, 41, 64, 8)
     img = device_raster(oracle, "mixed", Wd, Ht, 3, 3)
-    c = host_container(qb3, img, CF_H)
+    c = host_container(qb3, img, 0, CF_H)
     assert int(c[10]) == 5
-    check_fallback(qb3, c, as_rows(img, Ht), Layout(rects, 3), (2,), mask=0)
-    check_fallback(qb3, c, as_rows(img, Ht), Layout(rects, 3), (2,), mask=W16.QB3X_WINK_U16)
+    check_fallback(qb3, c, as_rows(img, Ht), Layout(rects, 3, 1, "cf8"), (2,), mask=0)
+    check_fallback(qb3, c, as_rows(img, Ht), Layout(rects, 3, 1, "cf8"), (2,), mask=W16.QB3X_WINK_U16)
     img2 = device_raster(oracle, "mixed", Wd, Ht, 2, 3)
-    check_fallback(qb3, host_container(qb3, img2, CF_H), as_rows(img2, Ht), Layout(rects, 2), (2,))
+    check_fallback(qb3, host_container(qb3, img2, 0, CF_H), as_rows(img2, Ht), Layout(rects, 2, 1, "cf8"), (2,), BIT)
     zeros = torch.zeros((Ht, Wd, 3), dtype=torch.uint8, device="cuda")
-    c = host_container(qb3, zeros, BEST)
+    c = host_container(qb3, zeros, 0, BEST)
     assert int(c[10]) == 7
-    check_fallback(qb3, c, as_rows(zeros, Ht), Layout(rects, 3), (3,))
+    check_fallback(qb3, c, as_rows(zeros, Ht), Layout(rects, 3, 1, "cf8"), (3,), BIT)
     noise = oracle.generate(Wd, Ht, 3, 0, "RANDOM", 5)
     s = np.asarray(oracle.encode(noise, 0, CF_H), np.uint8)
-    lay = Layout(rects, 3)
+    lay = Layout(rects, 3, 1, "cf8")
     asked = []
     for mask in (0, BIT):
         src, p, _ = open_source(qb3, s, mask)
@@ -318,20 +248,20 @@ def test_damaged_tables_cost_time_and_bytes(qb3, oracle, bands):
     Wd, Ht = 1001, 259
     img = device_raster(oracle, "mixed", Wd, Ht, bands, 5)
     rows = as_rows(img, Ht)
-    c = host_container(qb3, img, CF_H)
+    c = host_container(qb3, img, 0, CF_H)
     assert int(c[10]) == 5
-    tab = RB.Table(c).shape(bands)
+    tab = R.Table(c).shape(R.entry_bytes("cf8", bands), R.HEAD_FLAGS)
     nbx = (Wd + 3) // 4
     seg = (6 * nbx + 10) // 64 + 1                      # the second segment of block row 6 from column 10
     holds = [(40, 24, 300, 40), (120, 20, 120, 8)]
     beside = [(600, 24, 100, 4), (5, 200, 50, 50)]
     assert all(seg in segments_of(Wd, Ht, r) for r in holds) and not any(seg in segments_of(Wd, Ht, r) for r in beside)
     e0 = tab.entry_offset(seg)
-    lay = Layout(holds + beside, bands)
+    lay = Layout(holds + beside, bands, 1, "cf8")
     for at in (e0 + WB.field_at(bands, 9), e0 + 7, tab.chunks[0][0] + 6):          # unsealed: a field, an entering value, the check itself
         bad = c.copy()
         bad[at] ^= 0x10
-        check_fallback(qb3, bad, rows, lay, (3,))
+        check_fallback(qb3, bad, rows, lay, (3,), BIT)
 
     def longer(b):                          # block 5's length + 1
         at = e0 + WB.field_at(bands, 5)
@@ -348,26 +278,26 @@ def test_damaged_tables_cost_time_and_bytes(qb3, oracle, bands):
         change(bad)
         assert not np.array_equal(bad, c)
         R.seal(bad, tab.chunks[seg // tab.N][0])
-        src, p, _ = open_source(qb3, bad)
-        one = Layout(holds[:1], bands)                  # singly: the window falls back, from the whole container
+        src, p, _ = open_source(qb3, bad, BIT)
+        one = Layout(holds[:1], bands, 1, "cf8")                  # singly: the window falls back, from the whole container
         hb = np.full(one.size, SENTINEL, np.uint8)
         assert host_call(qb3, p, one, hb) == 1, what
         check_host(one, hb, rows)
         assert paths(qb3, p, 1) == [3] and src.log.count((0, len(c))) == 1 and not src.outside, what
-        assert counters(qb3, p)[0] == RB.plan_bytes(Wd, Ht, holds[:1], tab)[0] + len(c), what
-        one = Layout(beside[:1], bands)                 # ... and a window beside the damage does not
+        assert counters(qb3, p)[0] == R.plan_bytes(Wd, Ht, holds[:1], tab)[0] + len(c), what
+        one = Layout(beside[:1], bands, 1, "cf8")                 # ... and a window beside the damage does not
         hb = np.full(one.size, SENTINEL, np.uint8)
         del src.log[:]
         assert host_call(qb3, p, one, hb) == 1 and paths(qb3, p, 1) == [1] and (0, len(c)) not in src.log, what
         check_host(one, hb, rows)
         L.qb3_destroy_decoder(p)
-        src, p, _ = open_source(qb3, bad)               # inside a batch, device and host destinations
-        buf = device_buffer(lay)
+        src, p, _ = open_source(qb3, bad, BIT)               # inside a batch, device and host destinations
+        buf = lay.buffer()
         assert device_call(qb3, p, lay, buf) == len(lay.rects), what
         lay.check(buf, rows)
         assert paths(qb3, p, len(lay.rects)) == [3] * len(holds) + [1] * len(beside), what
         assert src.log.count((0, len(c))) == 1 and not src.outside
-        assert counters(qb3, p)[0] == RB.plan_bytes(Wd, Ht, lay.rects, tab)[0] + len(c), what
+        assert counters(qb3, p)[0] == R.plan_bytes(Wd, Ht, lay.rects, tab)[0] + len(c), what
         del src.log[:]
         hbuf = np.full(lay.size, SENTINEL, np.uint8)
         assert host_call(qb3, p, lay, hbuf) == len(lay.rects), what
@@ -387,13 +317,13 @@ def test_truncated_stream(qb3, oracle, bands):
     Wd, Ht = SMALLEST
     assert Wd % 4 == 0 and Ht % 4 == 0
     img = device_raster(oracle, "mixed", Wd, Ht, bands, 4)
-    c = host_container(qb3, img, BEST)
+    c = host_container(qb3, img, 0, BEST)
     assert int(c[10]) == 5
-    tab = RB.Table(c).shape(bands)
+    tab = R.Table(c).shape(R.entry_bytes("cf8", bands), R.HEAD_FLAGS)
     assert tab.K == 6
     rects = [(8, 8, 200, 8)] + W16.windows(Wd, Ht, 6, 64, 8)
     assert segments_of(Wd, Ht, rects[0]) == {2, 3}
-    lay = Layout(rects, bands)
+    lay = Layout(rects, bands, 1, "cf8")
     cuts = (tab.D + (tab.pos(1) + tab.pos(2)) // 16, tab.D + (tab.pos(3) + tab.pos(4)) // 16, tab.D + tab.pos(5) // 8 + 5, len(c) - 3)
     assert tab.D < cuts[0] < tab.D + tab.pos(2) // 8 <= tab.D + tab.pos(3) // 8 < cuts[1] < tab.D + tab.pos(4) // 8 < cuts[2] < len(c)
     for cut in cuts:
@@ -404,7 +334,7 @@ def test_truncated_stream(qb3, oracle, bands):
         n_ref = L.qb3x_read_windows(ref, qb3.window_array(rects, [want.ctypes.data + o for o in lay.offs], lay.strides()), len(rects))
         ref_paths = [L.qb3x_window_path(ref, i) for i in range(len(rects))]
         L.qb3_destroy_decoder(ref)
-        src, p, _ = open_source(qb3, short)
+        src, p, _ = open_source(qb3, short, BIT)
         hbuf = np.full(lay.size, SENTINEL, np.uint8)
         assert host_call(qb3, p, lay, hbuf) == n_ref, cut
         assert [bool(v) for v in paths(qb3, p, len(rects))] == [bool(v) for v in ref_paths]
@@ -426,18 +356,18 @@ def test_a_small_window_reads_a_small_part(qb3):
     L = qb3.lib
     Wd, Ht, b = 2051, 1030, 4
     img = synth.generate(Wd, Ht, b, 0, "NOISY3", 9)
-    c = host_container(qb3, img, BEST)
+    c = host_container(qb3, img, 0, BEST)
     assert int(c[10]) == 5 and len(c) >= 3 << 20
-    tab = RB.Table(c).shape(b)
+    tab = R.Table(c).shape(R.entry_bytes("cf8", b), R.HEAD_FLAGS)
     r = ((Wd - 64) // 2, (Ht - 64) // 2, 64, 64)
     cap_dw = (64 * b * 176 + 31) // 32 + 2
-    bound = 17 * 2 * cap_dw * 4 + 3 * (RB.CHUNK_MAX + R.IX_PAD + 2)
-    assert W.brute_segments(Wd, Ht, *r) <= 17 * 2 and len(RB.plan_chunks(Wd, Ht, [r], tab.K, tab.N)) <= 3
-    want = RB.plan_bytes(Wd, Ht, [r], tab)
+    bound = 17 * 2 * cap_dw * 4 + 3 * (R.CHUNK_MAX + R.IX_PAD + 2)
+    assert W.brute_segments(Wd, Ht, *r) <= 17 * 2 and len(R.plan_chunks(Wd, Ht, [r], tab.K, tab.N)) <= 3
+    want = R.plan_bytes(Wd, Ht, [r], tab)
     print("plan %d bytes in %d reads, bound %d, container %d" % (want[0], want[1], bound, len(c)))
     assert want[0] <= bound < len(c) // 5
-    src, p, _ = open_source(qb3, c)
-    lay = Layout([r], b)
+    src, p, _ = open_source(qb3, c, BIT)
+    lay = Layout([r], b, 1, "cf8")
     hbuf = np.full(lay.size, SENTINEL, np.uint8)
     assert host_call(qb3, p, lay, hbuf) == 1 and L.qb3x_last_window_path(p) == 1
     check_host(lay, hbuf, as_rows(img, Ht))
@@ -452,7 +382,7 @@ def test_qb3window_reads_a_common_factor_file_in_pieces_with_K(qb3, oracle, tmp_
     import subprocess
     Wd, Ht, b = 260, 100, 3
     img = device_raster(oracle, "mixed", Wd, Ht, b, 3)
-    c = host_container(qb3, img, BEST)
+    c = host_container(qb3, img, 0, BEST)
     assert int(c[10]) == 5
     c.tofile(tmp_path / "a.qb3")
     x0, y0, w, h = 101, 37, 120, 40

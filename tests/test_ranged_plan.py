@@ -11,6 +11,7 @@ import pytest
 
 import qb3_ranged as R
 import qb3_window as W
+from qb3_window_dev import chunk_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FTL, BASE, STORED = 8, 4, 255
@@ -35,7 +36,7 @@ def with_table(c, bands, W_, H_):
         for j in range(here):
             body[j * E:j * E + 6] = (1000 * (k0 + j)).to_bytes(6, "little")
             body[j * E + 6:j * E + E] = bytes((7 * (k0 + j) + i) & 0xff for i in range(E - 6))
-        chk = R.chunk_check(body)
+        chk = chunk_check(body)
         run += b"ix" + bytes([ln & 255, ln >> 8, 3, 2, chk & 255, chk >> 8]) + (64).to_bytes(4, "little") + body + b"zz\x04\x00"
     return np.concatenate([c[:at], np.frombuffer(bytes(run), np.uint8), c[at:]])
 
@@ -132,7 +133,7 @@ def test_table_ranges_follow_the_rule(qb3, oracle, shape, bands):
     L = qb3.lib
     Wd, Ht = shape
     c = with_table(oracle.encode(oracle.generate(Wd, Ht, bands, 0, "NOISY3", 2), 0, FTL), bands, Wd, Ht)
-    tab = R.Table(c).shape(bands)
+    tab = R.Table(c).shape(R.entry_bytes("u8", bands))
     src = R.Source(qb3, c)
     p, _ = src.open(qb3)
     assert p and L.qb3x_decoder_table_entries(p) == tab.K

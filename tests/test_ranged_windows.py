@@ -3,7 +3,6 @@ window calls': every window is the crop of what the whole decode writes, nothing
 what the reader is asked for: the table chunks and the pieces of the stream the range rule of qb3x.h names, restated in
 qb3_ranged.py and computed from the container's own table -- and the whole container wherever the shortcut is not taken.
 Containers are written by this library at level 2 and held in a numpy buffer behind a reader that logs its calls."""
-import ctypes as C
 import os
 import sys
 
@@ -13,47 +12,12 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import qb3_ranged as R  # noqa: E402
 import qb3_window as W  # noqa: E402
-from test_window_batch import Layout, SENTINEL, as_rows, full_decode, make_container, to_device  # noqa: E402
+from qb3_ranged import check_fallback, check_host, counters, device_call, host_call, host_container  # noqa: E402
+from qb3_window_dev import FTL, BASE, BASE_Z, SENTINEL, Layout, as_rows, full_decode, paths, to_device  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-FTL, BASE, BASE_Z = 8, 4, 0
-_vp = C.c_void_p
 SHAPES = ((100, 100), (1000, 37), (1024, 260), (2051, 1030))
-
-
-def host_container(qb3, img, dt, mode, level=2, quanta=1):
-    d_c, n = make_container(qb3, img, dt, mode, level, quanta=quanta)
-    return d_c[:n].cpu().numpy()
-
-
-def host_call(qb3, p, lay, hbuf, sel=None):
-    """qb3x_read_windows_ranged of the layout's windows (or of window `sel` alone) into the host buffer; returns the count"""
-    ks = range(len(lay.rects)) if sel is None else [sel]
-    rects = [lay.rects[k] for k in ks]
-    strides = [0 if lay.sbytes[k] == lay.rects[k][2] * lay.pix else lay.sbytes[k] // lay.tsz for k in ks]
-    wins = qb3.window_array(rects, [hbuf.ctypes.data + lay.offs[k] for k in ks], strides)
-    return qb3.lib.qb3x_read_windows_ranged(p, wins, len(rects))
-
-
-def device_call(qb3, p, lay, buf):
-    import torch
-    n = qb3.lib.qb3x_decode_windows_ranged(p, lay.array(qb3, buf), len(lay.rects), _vp(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    return n
-
-
-def check_host(lay, hbuf, rows, skip=()):
-    import torch
-    lay.check(torch.from_numpy(hbuf).cuda(), rows, skip)
-
-
-def paths(qb3, p, n):
-    return [qb3.lib.qb3x_window_path(p, i) for i in range(n)]
-
-
-def counters(qb3, p):
-    return qb3.lib.qb3x_ranged_bytes(p), qb3.lib.qb3x_ranged_reads(p)
 
 
 # ---------------------------------------------------------------------------------------------------------------- parity
@@ -75,11 +39,11 @@ def test_windows_from_pieces(qb3, shape, bands):
     rects = W.windows(Wd, Ht, 5 * Wd + bands, 24)
     for turn, mode in enumerate((FTL, BASE, BASE_Z)):
         c = host_container(qb3, img, 0, mode)
-        tab = R.Table(c).shape(bands)
+        tab = R.Table(c).shape(R.entry_bytes("u8", bands))
         src = R.Source(qb3, c)
         p, dims = src.open(qb3)
         assert p and dims == (Wd, Ht, bands) and L.qb3_get_mode(p) == mode and L.qb3x_decoder_table_entries(p) == tab.K
-        lay = Layout(rects, bands, 1, turn)
+        lay = Layout(rects, bands, 1, "u8", start=turn)
         # single calls
         hbuf = np.full(lay.size, SENTINEL, np.uint8)
         cached = set()
@@ -114,7 +78,7 @@ def test_windows_from_pieces(qb3, shape, bands):
                 assert all(off >= tab.D // 4 * 4 and (off, n) not in ranges for off, n in src.log)
         # a positive gap: fewer reads, at least as many bytes, the same pixels (a window whose block rows lie apart in the stream)
         some = rects[5:] if Wd * Ht < 200000 else [r for r in rects if r[2] < Wd // 2][:8]
-        sub = Layout(some, bands, 1, turn)
+        sub = Layout(some, bands, 1, "u8", start=turn)
         got = {}
         for gap in (0, 64, 1 << 20):
             L.qb3x_set_ranged_gap(p, gap)
@@ -156,7 +120,7 @@ def test_quanta(qb3):
     src = R.Source(qb3, c)
     p, _ = src.open(qb3)
     rects = W.windows(Wd, Ht, 3, 12)
-    lay = Layout(rects, b, 1)
+    lay = Layout(rects, b, 1, "u8")
     hbuf = np.full(lay.size, SENTINEL, np.uint8)
     assert host_call(qb3, p, lay, hbuf) == len(rects)
     check_host(lay, hbuf, want.view(Ht, -1))
@@ -194,40 +158,16 @@ def test_python_interface(qb3, tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------------------- falling back
-def check_fallback(qb3, c, rows, Wd, Ht, pix, tsz, want_paths, rects=None):
-    """host and device destinations: all windows written and exact, on the paths named, and the whole container read, once"""
-    L = qb3.lib
-    rects = W.windows(Wd, Ht, 41, 8) if rects is None else rects
-    lay = Layout(rects, pix, tsz)
-    src = R.Source(qb3, c)
-    p, _ = src.open(qb3)
-    assert p
-    for dev in (False, True):
-        del src.log[:]
-        if dev:
-            buf = lay.buffer()
-            assert device_call(qb3, p, lay, buf) == len(rects), qb3.last_error()
-            lay.check(buf, rows)
-        else:
-            hbuf = np.full(lay.size, SENTINEL, np.uint8)
-            assert host_call(qb3, p, lay, hbuf) == len(rects), qb3.last_error()
-            check_host(lay, hbuf, rows)
-        assert set(paths(qb3, p, len(rects))) <= set(want_paths), paths(qb3, p, len(rects))
-        assert L.qb3x_ranged_bytes(p) >= len(c)
-        assert src.log.count((0, len(c))) == 1 and not src.outside
-    L.qb3_destroy_decoder(p)
-
-
 def test_rasters_and_tables_the_shortcut_does_not_take(qb3, oracle):
     import torch
     from qb3_amd import synth
     img = synth.generate(1000, 520, 4, 2, "LANDSAT16", 3)                  # uint16 x 4, level 2: the strips of path 2
-    check_fallback(qb3, host_container(qb3, img, 2, FTL), as_rows(img, 520), 1000, 520, 8, 2, (2,))
+    check_fallback(qb3, host_container(qb3, img, 2, FTL), as_rows(img, 520), Layout(W.windows(1000, 520, 41, 8), 8, 2, "u8"), (2,))
     img = synth.generate(1000, 300, 3, 0, "NOISY3", 5)                      # a level-1 table
-    check_fallback(qb3, host_container(qb3, img, 0, FTL, level=1), as_rows(img, 300), 1000, 300, 3, 1, (3,))
+    check_fallback(qb3, host_container(qb3, img, 0, FTL, level=1), as_rows(img, 300), Layout(W.windows(1000, 300, 41, 8), 3, 1, "u8"), (3,))
     himg = oracle.generate(509, 259, 3, 0, "NOISY3", 5)                     # a plain container
     s = oracle.encode(himg, 0, FTL)
-    check_fallback(qb3, s, torch.from_numpy(himg.reshape(259, -1)).cuda(), 509, 259, 3, 1, (3,))
+    check_fallback(qb3, s, torch.from_numpy(himg.reshape(259, -1)).cuda(), Layout(W.windows(509, 259, 41, 8), 3, 1, "u8"), (3,))
 
 
 def test_damaged_tables_cost_time_and_bytes(qb3):
@@ -240,7 +180,7 @@ def test_damaged_tables_cost_time_and_bytes(qb3):
     img = synth.generate(Wd, Ht, b, 0, "NOISY3", 77)
     rows = as_rows(img, Ht)
     c = host_container(qb3, img, 0, FTL)
-    tab = R.Table(c).shape(b)
+    tab = R.Table(c).shape(R.entry_bytes("u8", b))
     nbx = Wd // 4
     seg = (24 // 4) * nbx // 64 + 1                  # block row 6, blocks 64..127: pixels x 256..511, y 24..27
     holds = [(40, 24, 300, 40), (300, 26, 8, 1), (256, 20, 256, 8)]
@@ -249,16 +189,16 @@ def test_damaged_tables_cost_time_and_bytes(qb3):
     for at in (e0 + 7, e0 + 6 + 2 * b + 11, tab.chunks[0][0] + 6, tab.chunks[-1][0] + tab.chunks[-1][1] - 1):
         bad = c.copy()
         bad[at] ^= 0x10
-        check_fallback(qb3, bad, rows, Wd, Ht, b, 1, (3,), holds + beside)
+        check_fallback(qb3, bad, rows, Layout(holds + beside, b, 1, "u8"), (3,))
     for moved in (tab.pos(seg) + 40, tab.pos(seg + 2), tab.pos(seg - 3), tab.pos(seg + 1) + 8 * 4096, (1 << 48) - 1):
         bad = c.copy()
         bad[e0:e0 + 6] = np.frombuffer(int(moved).to_bytes(6, "little"), np.uint8)
         R.seal(bad, tab.chunks[0][0])
-        check_fallback(qb3, bad, rows, Wd, Ht, b, 1, (3,), holds)
+        check_fallback(qb3, bad, rows, Layout(holds, b, 1, "u8"), (3,))
         # ... and the windows beside the moved entry keep their shortcut
         src = R.Source(qb3, bad)
         p, _ = src.open(qb3)
-        lay = Layout(holds + beside, b, 1)
+        lay = Layout(holds + beside, b, 1, "u8")
         buf = lay.buffer()
         assert device_call(qb3, p, lay, buf) == len(lay.rects)
         lay.check(buf, rows)
@@ -273,9 +213,9 @@ def test_truncated_stream(qb3):
     Wd, Ht, b = 1000, 300, 3
     img = synth.generate(Wd, Ht, b, 0, "NOISY3", 4)
     c = host_container(qb3, img, 0, BASE)
-    tab = R.Table(c).shape(b)
+    tab = R.Table(c).shape(R.entry_bytes("u8", b))
     rects = W.windows(Wd, Ht, 6, 8)
-    lay = Layout(rects, b, 1)
+    lay = Layout(rects, b, 1, "u8")
     for cut in (tab.D + tab.pos(tab.K - 1) // 8 + 30, tab.D + tab.pos(tab.K - 2) // 8 - 5, len(c) - 3):
         short = c[:cut].copy()
         strides = [0 if sb == r[2] * b else sb for sb, r in zip(lay.sbytes, rects)]

@@ -8,7 +8,6 @@ must give the same bytes by path 2 and count the segments of the window's block 
 Which value decoder a unit takes -- the code rule for rungs of 8 and above (px16_groups_hi), the 8-bit table below -- follows from
 the generators: test_window16_plan.py::test_the_generators_reach_both_value_decoders restates the rungs of their rasters on the CPU
 from the oracle's generator output and finds every raster of LANDSAT16 and DEM on both sides (NOISY3: the low amplitude)."""
-import ctypes as C
 import os
 import sys
 
@@ -18,83 +17,13 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import qb3_window as W  # noqa: E402
 import qb3_window16 as W16  # noqa: E402
+from qb3_window_dev import (FTL, BASE, BASE_Z, CF_H, SENTINEL, Layout, as_rows, batch_call, chunk_check, count, destination,  # noqa: E402
+                            full_decode, make_container, segment_size, table_chunks, window_call)
 
 pytestmark = pytest.mark.gpu
 
-FTL, BASE, BASE_Z, CF_H = 8, 4, 0, 5
 U16, I16 = W16.U16, W16.I16
 BIT = W16.QB3X_WINK_U16
-SENTINEL = 0xc3
-_vp = C.c_void_p
-
-
-def make_container(qb3, img, dt, mode, level=2, cband=None, quanta=1, want_index=False):
-    """a container in device memory, written by this library from a device raster (h, w, bands) with qb3x_set_encoder_index_chunk
-    (p, level); returns (uint8 tensor, size, out-of-band index or None)"""
-    import torch
-    from qb3_amd import device as qdev
-    h, w, b = img.shape
-    enc = qdev.DeviceEncoder(w, h, b, dt, mode=mode, cband=cband, want_index=want_index, index_chunk=level)
-    if quanta > 1:
-        assert qb3.lib.qb3_set_encoder_quanta(enc.p, quanta, False)
-    dst, n, index = enc.encode(img.reshape(-1))
-    out = torch.zeros((n + 3) // 4 * 4 + 64, dtype=torch.uint8, device=img.device)
-    out[:n] = dst[:n]
-    index = index.clone() if index is not None else None
-    enc.close()
-    return out, n, index
-
-
-def as_rows(t, h):
-    import torch
-    return t.contiguous().view(torch.uint8).reshape(h, -1)
-
-
-def full_decode(qb3, d_c, n):
-    """qb3x_decode_device on a handle of its own: the flat uint8 tensor, or None when the call fails"""
-    import torch
-    from qb3_amd import device as qdev
-    dec = qdev.DeviceDecoder(d_c, n)
-    out = torch.zeros(dec.out_bytes, dtype=torch.uint8, device=d_c.device)
-    got = qb3.lib.qb3x_decode_device(dec.p, _vp(d_c.data_ptr()), _vp(out.data_ptr()), None, _vp(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    dec.close()
-    return out if got else None
-
-
-def window_call(qb3, dec, d_c, win, want_rows, pix, k, index=None, tsz=2):
-    """one qb3x_decode_window_device into a sentinel-filled buffer.  k chooses the destination: it starts k % 8 halfwords into the
-    buffer (behind 16 sentinel bytes) and its rows are tight (k % 3 == 0), an even number of values wider (1) or an odd number (2).
-    Checks payload and sentinels; want_rows None: the call is expected to fail.  Returns the bytes written"""
-    import torch
-    x0, y0, w, h = win
-    wline = w * pix
-    extra = (0, 2 * (1 + k % 5), 1 + 2 * (k % 4))[k % 3]           # values
-    sbytes = wline + tsz * extra
-    addr = 16 + 2 * (k % 8)
-    buf = torch.full((addr + (h + 1) * sbytes + 64,), SENTINEL, dtype=torch.uint8, device=d_c.device)
-    n = qb3.lib.qb3x_decode_window_device(dec.p, _vp(d_c.data_ptr()), _vp(index.data_ptr()) if index is not None else None, x0, y0, w, h,
-                                          _vp(buf.data_ptr() + addr), sbytes // tsz if extra else 0, _vp(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    rows = buf[addr:addr + h * sbytes].view(h, sbytes)
-    if want_rows is None:
-        rows[:, :wline] = SENTINEL
-        assert n == 0 and bool((buf == SENTINEL).all())
-        return 0
-    assert n == h * wline, (win, n, qb3.last_error())
-    want = want_rows[y0:y0 + h, x0 * pix:(x0 + w) * pix]
-    if not torch.equal(rows[:, :wline], want):
-        bad = (rows[:, :wline] != want).nonzero()
-        raise AssertionError("window %r (destination %d): %d bytes differ, the first at row %d byte %d" % (win, k, len(bad), int(bad[0][0]), int(bad[0][1])))
-    rows[:, :wline] = SENTINEL
-    assert bool((buf == SENTINEL).all()), "window %r (destination %d): bytes outside the window were written" % (win, k)
-    return n
-
-
-def segment_size(qb3, dec):
-    bps = C.c_size_t()
-    qb3.lib.qb3x_window_segments(dec.p, 0, 0, dec.w, dec.h, C.byref(bps))
-    return bps.value
 
 
 def check_windows(qb3, dec, d_c, rows, Wd, Ht, pix, wins, k0=0):
@@ -103,11 +32,11 @@ def check_windows(qb3, dec, d_c, rows, Wd, Ht, pix, wins, k0=0):
     bps = segment_size(qb3, dec)
     for i, win in enumerate(wins):
         dec.set_window_kernels(BIT)
-        window_call(qb3, dec, d_c, win, rows, pix, k0 + i)
+        window_call(qb3, dec, d_c, win, rows, pix, 2, *destination("u16", k0 + i, 2))
         assert L.qb3x_last_window_path(dec.p) == 1 and L.qb3x_last_decode_status(dec.p) == 0, win
         assert L.qb3x_last_window_segments(dec.p) == L.qb3x_window_segments(dec.p, *win, None) == W.brute_segments(Wd, Ht, *win, bps=bps), win
         dec.set_window_kernels(0)
-        window_call(qb3, dec, d_c, win, rows, pix, k0 + i)
+        window_call(qb3, dec, d_c, win, rows, pix, 2, *destination("u16", k0 + i, 2))
         assert L.qb3x_last_window_path(dec.p) == 2, win
         assert L.qb3x_last_window_segments(dec.p) == W.row_segments(Wd, Ht, win[1], win[3], bps), win
 
@@ -138,56 +67,6 @@ def test_window16_kernel(qb3, case):
             dec.close()
 
 
-class Layout:
-    """the destinations of a batch in one buffer: window k starts k % 8 halfwords behind a dword, rows tight, wide-even or wide-odd"""
-
-    def __init__(self, rects, pix, mosaic=None):
-        self.rects, self.pix = rects, pix
-        self.offs, self.sbytes = [], []
-        if mosaic:                          # the windows side by side in rows of one image `mosaic` values wide: (column, row) each
-            for (col, row) in mosaic[1]:
-                self.offs.append(16 + 2 * (row * mosaic[0] + col))
-                self.sbytes.append(2 * mosaic[0])
-            self.size = 16 + 2 * mosaic[0] * mosaic[2] + 64
-            return
-        at = 16
-        for k, (x0, y0, w, h) in enumerate(rects):
-            at = (at + 3) // 4 * 4 + 2 * (k % 8)
-            sb = w * pix + 2 * (0, 2 * (1 + k % 5), 1 + 2 * (k % 4))[k % 3]
-            self.offs.append(at)
-            self.sbytes.append(sb)
-            at += h * sb + 6
-        self.size = at + 64
-
-    def array(self, qb3, buf):
-        strides = [0 if sb == r[2] * self.pix else sb // 2 for sb, r in zip(self.sbytes, self.rects)]
-        return qb3.window_array(self.rects, [buf.data_ptr() + o for o in self.offs], strides)
-
-    def check(self, buf, want_rows):
-        import torch
-        buf = buf.clone()
-        for k, ((x0, y0, w, h), off, sb) in enumerate(zip(self.rects, self.offs, self.sbytes)):
-            rows = buf[off:off + h * sb].view(h, sb)
-            assert torch.equal(rows[:, :w * self.pix], want_rows[y0:y0 + h, x0 * self.pix:(x0 + w) * self.pix]), (k, self.rects[k])
-            rows[:, :w * self.pix] = SENTINEL
-        assert bool((buf == SENTINEL).all()), "bytes outside the windows were written"
-
-
-def batch_call(qb3, dec, d_c, lay, host=None):
-    """qb3x_decode_windows_device (host: qb3x_read_windows over the container's host copy) into a fresh sentinel buffer"""
-    import torch
-    if host is not None:
-        hbuf = np.full(lay.size, SENTINEL, np.uint8)
-        strides = [0 if sb == r[2] * lay.pix else sb // 2 for sb, r in zip(lay.sbytes, lay.rects)]
-        wins = qb3.window_array(lay.rects, [hbuf.ctypes.data + o for o in lay.offs], strides)
-        n = qb3.lib.qb3x_read_windows(host, wins, len(lay.rects))
-        return n, torch.from_numpy(hbuf).cuda()
-    buf = torch.full((lay.size,), SENTINEL, dtype=torch.uint8, device="cuda")
-    n = qb3.lib.qb3x_decode_windows_device(dec.p, _vp(d_c.data_ptr()), None, lay.array(qb3, buf), len(lay.rects), _vp(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    return n, buf
-
-
 @pytest.mark.parametrize("case", ((4, 1001, 259, BASE, "DEM"), (8, 1001, 259, FTL, "LANDSAT16"), (6, 132, 37, BASE_Z, "DEM"), (1, 260, 37, FTL, "LANDSAT16")),
                          ids=lambda c: "%d-%dx%d-m%d" % c[:4])
 def test_window16_batch(qb3, case):
@@ -206,7 +85,7 @@ def test_window16_batch(qb3, case):
     host = d_c[:n].cpu().numpy() if bands in (4, 8) else None
     for nwin in (1, 2, 65):
         rects = wins[5:5 + nwin] if nwin < 65 else wins[3:68]          # (random ones overlap each other and the fixed ones)
-        lay = Layout(rects, pix)
+        lay = Layout(rects, pix, 2, "u16")
         total = sum(W.brute_segments(Wd, Ht, *r, bps=bps) for r in rects)
         dec.set_window_kernels(BIT)
         got, buf = batch_call(qb3, dec, d_c, lay)
@@ -233,7 +112,7 @@ def test_window16_batch(qb3, case):
     # a mosaic: 3 x 2 tiles of 40 x 20 pixels from six places of the raster, side by side in one image of 120 x 40 pixels
     tw, th = min(40, Wd // 3), min(20, Ht // 2)
     rects = [((7 + 31 * i) % (Wd - tw), (5 + 13 * i) % (Ht - th), tw, th) for i in range(6)]
-    lay = Layout(rects, pix, mosaic=(3 * tw * bands, [((i % 3) * tw * bands, (i // 3) * th) for i in range(6)], 2 * th))
+    lay = Layout(rects, pix, 2, "u16", mosaic=(3 * tw * bands, [((i % 3) * tw * bands, (i // 3) * th) for i in range(6)], 2 * th))
     dec.set_window_kernels(BIT)
     got, buf = batch_call(qb3, dec, d_c, lay)
     assert got == 6 and all(L.qb3x_window_path(dec.p, i) == 1 for i in range(6))
@@ -252,30 +131,17 @@ def test_window16_dequantises_the_window(qb3):
     Wd, Ht, b = 260, 37, 4
     img = synth.generate(Wd, Ht, b, U16, "LANDSAT16", 11)
     d_c, n, _ = make_container(qb3, img, U16, BASE, 2, quanta=3)
-    want = full_decode(qb3, d_c, n)
+    want = full_decode(qb3, d_c, n)[0]
     assert want is not None and not torch.equal(want, img.reshape(-1).view(torch.uint8))
     dec = qdev.DeviceDecoder(d_c, n)
     dec.set_window_kernels(BIT)
     for i, win in enumerate(W16.windows(Wd, Ht, 3, 64, 8)):
-        window_call(qb3, dec, d_c, win, want.view(Ht, -1), 2 * b, i)
+        window_call(qb3, dec, d_c, win, want.view(Ht, -1), 2 * b, 2, *destination("u16", i, 2))
         assert qb3.lib.qb3x_last_window_path(dec.p) == 1
     dec.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------- trust
-def table_chunks(c):
-    """[(offset of an "ix" chunk, its length)] and the offset of the first stream byte"""
-    c = bytes(c)
-    pos, out = 11, []
-    while True:
-        sig, ln = c[pos:pos + 2], c[pos + 2] | c[pos + 3] << 8
-        if sig == b"DT":
-            return out, pos + 2
-        if sig == b"ix":
-            out.append((pos, ln))
-        pos += ln if sig in (b"ix", b"zz") else 4 + ln
-
-
 @pytest.mark.parametrize("bands", (4, 8, 1))
 def test_damaged_tables_and_short_streams_cost_time_not_pixels(qb3, bands):
     """a flipped entry byte (the chunk's check), a changed lane length under a re-sealed check (the kernel's own test of where a
@@ -306,10 +172,10 @@ def test_damaged_tables_and_short_streams_cost_time_not_pixels(qb3, bands):
         return chunks[k // per_chunk][0] + 12 + (k % per_chunk) * E
 
     def expect_path3(bad, size, what):
-        want = full_decode(qb3, bad, size)
+        want = full_decode(qb3, bad, size)[0]
         dec = qdev.DeviceDecoder(bad, size)
         dec.set_window_kernels(BIT)
-        window_call(qb3, dec, bad, win, None if want is None else want.view(Ht, -1), 2 * bands, 3)
+        window_call(qb3, dec, bad, win, None if want is None else want.view(Ht, -1), 2 * bands, 2, *destination("u16", 3, 2))
         if want is not None:
             assert L.qb3x_last_window_path(dec.p) == 3, what
         dec.close()
@@ -318,7 +184,7 @@ def test_damaged_tables_and_short_streams_cost_time_not_pixels(qb3, bands):
     # the sound container first: path 1
     dec = qdev.DeviceDecoder(d_c, n)
     dec.set_window_kernels(BIT)
-    window_call(qb3, dec, d_c, win, rows, 2 * bands, 3)
+    window_call(qb3, dec, d_c, win, rows, 2 * bands, 2, *destination("u16", 3, 2))
     assert L.qb3x_last_window_path(dec.p) == 1
     dec.close()
     e0 = entry_at(seg)
@@ -336,8 +202,8 @@ def test_damaged_tables_and_short_streams_cost_time_not_pixels(qb3, bands):
     v = (v & ~(1023 << bit)) | (((f + 1) & 1023) << bit)
     bad[fields:fields + nf] = np.frombuffer(v.to_bytes(nf, "little"), np.uint8)
     c0, cl = chunks[seg // per_chunk]
-    s16 = W16.seal(bad[c0 + 12:c0 + cl])
-    assert W16.seal(host[c0 + 12:c0 + cl]) == int(host[c0 + 6]) | int(host[c0 + 7]) << 8      # (the formula is the encoder's)
+    s16 = chunk_check(bad[c0 + 12:c0 + cl])
+    assert chunk_check(host[c0 + 12:c0 + cl]) == int(host[c0 + 6]) | int(host[c0 + 7]) << 8      # (the formula is the encoder's)
     bad[c0 + 6], bad[c0 + 7] = s16 & 255, s16 >> 8
     d_bad = torch.zeros_like(d_c)
     d_bad[:n] = torch.from_numpy(bad).cuda()
@@ -365,21 +231,18 @@ def test_not_taken_with_the_bit_set(qb3):
         d_c, n, index = make_container(qb3, img, dt, mode, level, want_index=want_index)
         dec = qdev.DeviceDecoder(d_c, n)
         dec.set_window_kernels(BIT)
-        window_call(qb3, dec, d_c, win, as_rows(img, img.shape[0]), pix, 1, index, tsz=1 if dt == 0 else 2)
+        tsz = 1 if dt == 0 else 2
+        window_call(qb3, dec, d_c, win, as_rows(img, img.shape[0]), pix, tsz, *destination("u16", 1, tsz), index)
         assert L.qb3x_last_window_path(dec.p) == path, (dt, mode, level)
         dec.close()
-
-    def count(name):
-        ms, cnt = C.c_double(), C.c_uint64()
-        return cnt.value if L.qb3x_profile_get(name.encode(), C.byref(ms), C.byref(cnt)) else 0
 
     L.qb3x_profile_enable(1)
     L.qb3x_profile_reset()
     try:
         one(synth.generate(260, 37, 3, 0, "NOISY3", 1), 0, FTL, 2, 1, 3)
-        assert count("dec_window") == 1 and count("dec_window16") == 0
+        assert count(qb3, "dec_window") == 1 and count(qb3, "dec_window16") == 0
         one(synth.generate(260, 37, 4, U16, "LANDSAT16", 1), U16, FTL, 2, 1, 8)
-        assert count("dec_window") == 1 and count("dec_window16") == 1
+        assert count(qb3, "dec_window") == 1 and count(qb3, "dec_window16") == 1
     finally:
         L.qb3x_profile_enable(0)
     one(synth.generate(260, 37, 5, U16, "LANDSAT16", 1), U16, FTL, 2, 2, 10)

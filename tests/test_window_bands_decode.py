@@ -16,6 +16,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import qb3_window as W  # noqa: E402
 import qb3_window16 as W16  # noqa: E402
+import qb3_window_dev as D  # noqa: E402
 import qb3_window_unit as WU  # noqa: E402
 import qb3_window_best as WBEST  # noqa: E402
 import qb3_window_best_unit as WBU  # noqa: E402
@@ -73,18 +74,18 @@ def test_fused_route_unit(qb3, case):
             gen = WU.GENERATORS[g % 3]
             g += 1
             img = synth.generate(Wd, Ht, bands, dt, gen, 31 * bands + Wd)
-            d_c, n, _ = WU.make_container(qb3, img, dt, mode, 2, cband)
+            d_c, n, _ = D.make_container(qb3, img, dt, mode, 2, cband)
             dec = qdev.DeviceDecoder(d_c, n)
             if L.qb3_get_mode(dec.p) == 255:
                 dec.close()
                 continue
             dec.set_window_kernels(UNIT)
-            bps = WU.segment_size(qb3, dec)
+            bps = D.segment_size(qb3, dec)
             assert bps == WU.seg_blocks(bands)
             rects = W16.windows(Wd, Ht, 5 * Wd + bands + mode, bps, 1)
             assert 8 <= len(rects) <= 12
             total = sum(W.brute_segments(Wd, Ht, *r, bps=bps) for r in rects)
-            rows = WU.as_rows(img, Ht)
+            rows = D.as_rows(img, Ht)
             for sel in WB.selections(bands):
                 call_and_check(qb3, dec, d_c, rows, bands, tsz, rects, sel, 1, 0, segs=total)
                 assert L.qb3x_last_decode_status(dec.p) == 0
@@ -108,17 +109,17 @@ def test_fused_route_common_factor(qb3, case):
             name = WBU.SIGNAL[k % 3]
             k += 1
             img = WBU.device_raster(name, Wd, Ht, bands, dt, 31 * bands + Wd)
-            d_c, n, _ = WU.make_container(qb3, img, dt, mode, 2)
+            d_c, n, _ = D.make_container(qb3, img, dt, mode, 2)
             dec = qdev.DeviceDecoder(d_c, n)
             if L.qb3_get_mode(dec.p) == 255 or (mode == BEST and L.qb3_get_mode(dec.p) == 7):
                 dec.close()
                 continue
             assert L.qb3_get_mode(dec.p) == CF_H
             dec.set_window_kernels(CFU)
-            bps = WU.segment_size(qb3, dec)
+            bps = D.segment_size(qb3, dec)
             rects = W16.windows(Wd, Ht, 5 * Wd + bands + mode, bps, 1)
             total = sum(W.brute_segments(Wd, Ht, *r, bps=bps) for r in rects)
-            rows = WU.as_rows(img, Ht)
+            rows = D.as_rows(img, Ht)
             for sel in WB.selections(bands):
                 call_and_check(qb3, dec, d_c, rows, bands, tsz, rects, sel, 1, 0, segs=total)
                 assert L.qb3x_last_decode_status(dec.p) == 0
@@ -161,14 +162,14 @@ def test_gather_route_on_path_1(qb3, name):
     tsz = TSZ[dt]
     for (Wd, Ht) in ((260, 37), (201, 67)):
         img = make(Wd, Ht, bands, dt)
-        d_c, n, _ = WU.make_container(qb3, img, dt, mode, 2)
+        d_c, n, _ = D.make_container(qb3, img, dt, mode, 2)
         dec = qdev.DeviceDecoder(d_c, n)
         assert L.qb3_get_mode(dec.p) != 255
         dec.set_window_kernels(bits)
-        bps = WU.segment_size(qb3, dec)
+        bps = D.segment_size(qb3, dec)
         rects = W16.windows(Wd, Ht, Wd + bands, bps, 1)
         total = sum(W.brute_segments(Wd, Ht, *r, bps=bps) for r in rects)
-        rows = WU.as_rows(img, Ht)
+        rows = D.as_rows(img, Ht)
         for sel in sels:
             call_and_check(qb3, dec, d_c, rows, bands, tsz, rects, sel, 1, 1, segs=total, shift=shift)
             assert L.qb3x_last_decode_status(dec.p) == 0
@@ -182,10 +183,10 @@ def test_gather_route_on_paths_2_and_3(qb3):
     dt, bands, Wd, Ht = WU.I16, 7, 201, 67
     tsz = TSZ[dt]
     img = synth.generate(Wd, Ht, bands, dt, "DEM", 3)
-    rows = WU.as_rows(img, Ht)
+    rows = D.as_rows(img, Ht)
     rects = W16.windows(Wd, Ht, 11, WU.seg_blocks(bands), 1)
     for level, want_index, path in ((2, False, 2), (1, False, 3), (2, True, 3)):
-        d_c, n, index = WU.make_container(qb3, img, dt, FTL, level, want_index=want_index)
+        d_c, n, index = D.make_container(qb3, img, dt, FTL, level, want_index=want_index)
         dec = qdev.DeviceDecoder(d_c, n)
         dec.set_window_kernels(UNIT if path == 3 else 0)
         for k, sel in enumerate(([5], [6, 3, 0], [2, 2, 4, 2, 1, 0, 6, 5, 3])):
@@ -204,12 +205,12 @@ def test_batches_and_a_mosaic(qb3, case):
     dt, bands, bits, sel, gathers = case
     Wd, Ht, tsz, nsel = 201, 67, TSZ[dt], len(sel)
     img = synth.generate(Wd, Ht, bands, dt, "NOISY3", 77)
-    rows = WU.as_rows(img, Ht)
+    rows = D.as_rows(img, Ht)
     want = WB.select(rows, bands, tsz, sel)
-    d_c, n, _ = WU.make_container(qb3, img, dt, BASE, 2)
+    d_c, n, _ = D.make_container(qb3, img, dt, BASE, 2)
     dec = qdev.DeviceDecoder(d_c, n)
     dec.set_window_kernels(bits)
-    bps = WU.segment_size(qb3, dec)
+    bps = D.segment_size(qb3, dec)
     wins = W16.windows(Wd, Ht, 9, bps, 65)
     host = d_c[:n].cpu().numpy()
     for nwin in (1, 2, 65):
@@ -248,12 +249,12 @@ def test_quanta_commute_with_the_selection(qb3, case):
     dt, bands, bits, level, path, gathers = case
     Wd, Ht, tsz = 201, 67, TSZ[dt]
     img = synth.generate(Wd, Ht, bands, dt, "NOISY3", 11)
-    d_c, n, _ = WU.make_container(qb3, img, dt, BASE, level, quanta=3)
-    want = WU.full_decode(qb3, d_c, n)
+    d_c, n, _ = D.make_container(qb3, img, dt, BASE, level, quanta=3)
+    want = D.full_decode(qb3, d_c, n)[0]
     assert want is not None and not torch.equal(want, img.reshape(-1).view(torch.uint8))
     dec = qdev.DeviceDecoder(d_c, n)
     dec.set_window_kernels(bits)
-    rects = W16.windows(Wd, Ht, 3, WU.segment_size(qb3, dec), 1)
+    rects = W16.windows(Wd, Ht, 3, D.segment_size(qb3, dec), 1)
     for sel in ([bands - 1, 0], [1, 1, 0]):
         call_and_check(qb3, dec, d_c, want.view(Ht, -1), bands, tsz, rects, sel, path, gathers)
     dec.close()
@@ -269,10 +270,10 @@ def test_a_damaged_table_costs_time_not_pixels(qb3):
     dt, bands, Wd, Ht = WU.U8, 5, 1001, 259
     tsz = TSZ[dt]
     img = synth.generate(Wd, Ht, bands, dt, "DEM", 5)
-    rows = WU.as_rows(img, Ht)
-    d_c, n, _ = WU.make_container(qb3, img, dt, FTL, 2)
+    rows = D.as_rows(img, Ht)
+    d_c, n, _ = D.make_container(qb3, img, dt, FTL, 2)
     host = d_c[:n].cpu().numpy()
-    chunks, _ = WU.table_chunks(host)
+    chunks, _ = D.table_chunks(host)
     E = WU.entry_bytes(bands, tsz)
     per_chunk = (chunks[0][1] - 12) // E
     bps = WU.seg_blocks(bands)
@@ -290,7 +291,7 @@ def test_a_damaged_table_costs_time_not_pixels(qb3):
 
     def run(bad, paths, gathers):
         d_bad = upload(bad)
-        want = WU.full_decode(qb3, d_bad, n)
+        want = D.full_decode(qb3, d_bad, n)[0]
         assert want is not None and torch.equal(want.view(Ht, -1), rows)
         dec = qdev.DeviceDecoder(d_bad, n)
         dec.set_window_kernels(UNIT)
@@ -309,7 +310,7 @@ def test_a_damaged_table_costs_time_not_pixels(qb3):
     v = (v & ~(4095 << 60)) | (((f + 1) & 4095) << 60)
     bad[fields:fields + nf] = np.frombuffer(v.to_bytes(nf, "little"), np.uint8)
     c0, cl = chunks[seg // per_chunk]
-    s16 = W16.seal(bad[c0 + 12:c0 + cl])
+    s16 = D.chunk_check(bad[c0 + 12:c0 + cl])
     bad[c0 + 6], bad[c0 + 7] = s16 & 255, s16 >> 8
     run(bad, [3, 1], 1)
 
@@ -323,15 +324,15 @@ def test_the_identity_selection_is_the_full_band_call(qb3, case):
     dt, bands, bits = case
     Wd, Ht, tsz = 201, 67, TSZ[dt]
     img = synth.generate(Wd, Ht, bands, dt, "NOISY3", 4)
-    d_c, n, _ = WU.make_container(qb3, img, dt, FTL, 2)
+    d_c, n, _ = D.make_container(qb3, img, dt, FTL, 2)
     dec = qdev.DeviceDecoder(d_c, n)
     dec.set_window_kernels(bits)
-    rects = W16.windows(Wd, Ht, 21, WU.segment_size(qb3, dec), 1)
-    lay = WU.Layout(rects, bands * tsz, tsz)
-    got, full = WU.batch_call(qb3, dec, d_c, lay)
+    rects = W16.windows(Wd, Ht, 21, D.segment_size(qb3, dec), 1)
+    lay = D.Layout(rects, bands * tsz, tsz, "unit")
+    got, full = D.batch_call(qb3, dec, d_c, lay)
     assert got == len(rects)
     segs = L.qb3x_last_window_segments(dec.p)
-    lay2, buf = call_and_check(qb3, dec, d_c, WU.as_rows(img, Ht), bands, tsz, rects, list(range(bands)), 1, 0, segs=segs)
+    lay2, buf = call_and_check(qb3, dec, d_c, D.as_rows(img, Ht), bands, tsz, rects, list(range(bands)), 1, 0, segs=segs)
     assert lay2.offs == lay.offs and torch.equal(buf, full)
     dec.close()
 
@@ -342,7 +343,7 @@ def test_python_device_decoder_takes_bands(qb3):
     from qb3_amd import device as qdev, synth
     Wd, Ht, bands = 201, 67, 7
     img = synth.generate(Wd, Ht, bands, WU.I16, "DEM", 2)
-    d_c, n, _ = WU.make_container(qb3, img, WU.I16, FTL, 2)
+    d_c, n, _ = D.make_container(qb3, img, WU.I16, FTL, 2)
     dec = qdev.DeviceDecoder(d_c, n)
     rects = [(3, 5, 50, 20), (100, 40, 101, 27), (0, 0, Wd, Ht)]
     for bits, gathers in ((UNIT, 0), (0, 1)):

@@ -95,7 +95,7 @@ def test_argument_errors_refuse_the_whole_call(qb3, oracle):
 @pytest.mark.parametrize("dt,bands", ((0, 3), (3, 5)), ids=("u8x3", "i16x5"))
 def test_stored_windows_are_cropped_and_selected_on_the_host(qb3, oracle, dt, bands):
     """uint8 x 3 and int16 x 5, STORED: one band, a reversal, a selection with repeats and the identity; tight, wide-even and wide-odd
-    rows (WU.Layout), and a mosaic of four windows in one buffer.  No device is needed: path 3, no gather"""
+    rows (WB.Layout), and a mosaic of four windows in one buffer.  No device is needed: path 3, no gather"""
     L = qb3.lib
     img, s = stored_container(oracle, dt, bands)
     Ht, Wd = img.shape[:2]

@@ -12,123 +12,12 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import qb3_window as W  # noqa: E402
+from qb3_window_dev import (FTL, BASE, BASE_Z, CF_H, RLE, ZCURVE, SENTINEL, Layout, as_rows, batch_call, chunk_check,  # noqa: E402
+                            full_decode, make_container, paths, single_calls, table_chunks, to_device)
 
 pytestmark = pytest.mark.gpu
 
-FTL, BASE, BASE_Z, CF_H, RLE = 8, 4, 0, 5, 2
-ZCURVE = 0x0145236789cdabef
-SENTINEL = 0xc3
 _vp = C.c_void_p
-
-
-def make_container(qb3, img, dt, mode, level=2, cband=None, zorder=False, quanta=1):
-    """a container in device memory, written by this library from a device raster (h, w, bands); returns (uint8 tensor, size)"""
-    import torch
-    from qb3_amd import device as qdev
-    h, w, b = img.shape
-    enc = qdev.DeviceEncoder(w, h, b, dt, mode=mode, cband=cband, want_index=False, index_chunk=level)
-    if zorder:
-        qb3.lib.qb3_set_encoder_mode(enc.p, 0)          # the Z order sticks to the handle
-    if quanta > 1:
-        assert qb3.lib.qb3_set_encoder_quanta(enc.p, quanta, False)
-    dst, n, _ = enc.encode(img.reshape(-1))
-    out = torch.zeros((n + 3) // 4 * 4 + 64, dtype=torch.uint8, device=img.device)
-    out[:n] = dst[:n]
-    enc.close()
-    return out, n
-
-
-def to_device(host, pad=64):
-    import torch
-    out = torch.zeros((len(host) + 3) // 4 * 4 + pad, dtype=torch.uint8, device="cuda")
-    out[:len(host)] = torch.from_numpy(np.ascontiguousarray(host))
-    return out
-
-
-def as_rows(t, h):
-    import torch
-    return t.contiguous().view(torch.uint8).reshape(h, -1)
-
-
-def full_decode(qb3, d_c, n):
-    """qb3x_decode_device on a handle of its own: (flat uint8 tensor or None when the call fails, status)"""
-    import torch
-    from qb3_amd import device as qdev
-    dec = qdev.DeviceDecoder(d_c, n)
-    out = torch.zeros(dec.out_bytes, dtype=torch.uint8, device=d_c.device)
-    got = qb3.lib.qb3x_decode_device(dec.p, _vp(d_c.data_ptr()), _vp(out.data_ptr()), None, _vp(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    st = qb3.lib.qb3x_last_decode_status(dec.p)
-    dec.close()
-    return (out if got else None), st
-
-
-class Layout:
-    """the destinations of a batch packed into one buffer: window k starts at a byte offset with (offset % 4) == k % 4 -- every
-    alignment -- and its rows are tight (even k) or `extra` values wider (odd k); a few sentinel bytes lie between windows"""
-
-    def __init__(self, rects, pix, tsz, start=0):
-        self.rects, self.pix, self.tsz = rects, pix, tsz
-        self.offs, self.sbytes = [], []
-        at = 8
-        for k, (x0, y0, w, h) in enumerate(rects):
-            extra = 0 if (k + start) % 2 == 0 else (1 + (k * 7) % 29) * tsz
-            at = (at + 3) // 4 * 4 + ((k + start) % 4 if tsz == 1 else 0)
-            self.offs.append(at)
-            self.sbytes.append(w * pix + extra)
-            at += h * (w * pix + extra) + 5
-        self.size = at + 64
-
-    def buffer(self):
-        import torch
-        return torch.full((self.size,), SENTINEL, dtype=torch.uint8, device="cuda")
-
-    def array(self, qb3, buf):
-        strides = [0 if sb == r[2] * self.pix else sb // self.tsz for sb, r in zip(self.sbytes, self.rects)]
-        return qb3.window_array(self.rects, [buf.data_ptr() + o for o in self.offs], strides)
-
-    def check(self, buf, want_rows, skip=()):
-        """every window (but those in `skip`) equals the crop of want_rows, and nothing else in the buffer was written"""
-        import torch
-        buf = buf.clone()
-        for k, ((x0, y0, w, h), off, sb) in enumerate(zip(self.rects, self.offs, self.sbytes)):
-            rows = buf[off:off + h * sb].view(h, sb)
-            wline = w * self.pix
-            if k not in skip:
-                want = want_rows[y0:y0 + h, x0 * self.pix:(x0 + w) * self.pix]
-                if not torch.equal(rows[:, :wline], want):
-                    bad = (rows[:, :wline] != want).nonzero()
-                    raise AssertionError("window %d %r: %d bytes differ, the first at row %d byte %d" %
-                                         (k, self.rects[k], len(bad), int(bad[0][0]), int(bad[0][1])))
-            rows[:, :wline] = SENTINEL
-        assert bool((buf == SENTINEL).all()), "bytes outside the windows were written"
-
-
-def batch_call(qb3, dec, d_c, lay, buf=None, index=None):
-    """one qb3x_decode_windows_device into a fresh sentinel buffer; returns (windows written, buffer)"""
-    import torch
-    buf = lay.buffer() if buf is None else buf
-    wins = lay.array(qb3, buf)
-    n = qb3.lib.qb3x_decode_windows_device(dec.p, _vp(d_c.data_ptr()), _vp(index.data_ptr()) if index is not None else None,
-                                           wins, len(lay.rects), _vp(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    return n, buf
-
-
-def paths(qb3, dec, n):
-    return [qb3.lib.qb3x_window_path(dec.p, i) for i in range(n)]
-
-
-def single_calls(qb3, dec, d_c, lay):
-    """the same windows through n single calls into a second buffer of the same layout"""
-    import torch
-    buf = lay.buffer()
-    st = _vp(torch.cuda.current_stream().cuda_stream)
-    for (x0, y0, w, h), off, sb in zip(lay.rects, lay.offs, lay.sbytes):
-        stride = 0 if sb == w * lay.pix else sb // lay.tsz
-        assert qb3.lib.qb3x_decode_window_device(dec.p, _vp(d_c.data_ptr()), None, x0, y0, w, h, _vp(buf.data_ptr() + off), stride, st) == h * w * lay.pix
-    torch.cuda.synchronize()
-    return buf
 
 
 def profile_counts(qb3):
@@ -153,7 +42,7 @@ def test_one_launch_for_all_windows(qb3, shape, bands):
     k = 0
     for mode, sticky_z in cases:
         for cband in maps:
-            d_c, n = make_container(qb3, img, 0, mode, 2, cband, sticky_z)
+            d_c, n, _ = make_container(qb3, img, 0, mode, 2, cband, zorder=sticky_z)
             dec = qdev.DeviceDecoder(d_c, n)
             assert L.qb3_get_mode(dec.p) == mode and (L.qb3_get_order(dec.p) == ZCURVE) == (mode == BASE_Z or sticky_z)
             want = rows
@@ -163,12 +52,12 @@ def test_one_launch_for_all_windows(qb3, shape, bands):
                 want = full.view(Ht, -1)
             rects = W.windows(Wd, Ht, 5 * Wd + bands + mode, 40)
             assert len(rects) >= 45
-            lay = Layout(rects, bands, 1, k)
+            lay = Layout(rects, bands, 1, "u8", start=k)
             k += 1
             got, buf = batch_call(qb3, dec, d_c, lay)
             assert got == len(rects), qb3.last_error()
             lay.check(buf, want)
-            assert paths(qb3, dec, len(rects)) == [1] * len(rects)
+            assert paths(qb3, dec.p, len(rects)) == [1] * len(rects)
             assert all(L.qb3x_window_ok(dec.p, i) == 1 for i in range(len(rects)))
             assert L.qb3x_last_window_path(dec.p) == 1
             assert L.qb3x_last_window_segments(dec.p) == sum(W.brute_segments(Wd, Ht, *r) for r in rects)
@@ -187,7 +76,7 @@ def test_batch_sizes(qb3, count):
     L = qb3.lib
     Wd, Ht, b = 1000, 300, 3
     img = synth.generate(Wd, Ht, b, 0, "NOISY3", 4)
-    d_c, n = make_container(qb3, img, 0, BASE, 2)
+    d_c, n, _ = make_container(qb3, img, 0, BASE, 2)
     dec = qdev.DeviceDecoder(d_c, n)
     rng = np.random.default_rng(count)
     rects = []
@@ -200,11 +89,11 @@ def test_batch_sizes(qb3, count):
         else:
             w, h = int(rng.integers(1, 40)), int(rng.integers(1, 20))
             rects.append((int(rng.integers(0, Wd - w + 1)), int(rng.integers(0, Ht - h + 1)), w, h))
-    lay = Layout(rects, b, 1)
+    lay = Layout(rects, b, 1, "u8")
     got, buf = batch_call(qb3, dec, d_c, lay)
     assert got == count, qb3.last_error()
     lay.check(buf, as_rows(img, Ht))
-    assert paths(qb3, dec, count) == [1] * count
+    assert paths(qb3, dec.p, count) == [1] * count
     assert L.qb3x_window_path(dec.p, count) == 0
     assert L.qb3x_last_window_segments(dec.p) == sum(W.brute_segments(Wd, Ht, *r) for r in rects)
     dec.close()
@@ -218,7 +107,7 @@ def test_mosaic_and_one_launch(qb3):
     L = qb3.lib
     Wd, Ht, b = 4096, 2304, 3
     img = synth.generate(Wd, Ht, b, 0, "NOISY3", 12)
-    d_c, n = make_container(qb3, img, 0, FTL, 2)
+    d_c, n, _ = make_container(qb3, img, 0, FTL, 2)
     dec = qdev.DeviceDecoder(d_c, n)
     X0, Y0, R, T = 1001, 131, 2048, 256
     rects = [(X0 + T * i, Y0 + T * j, T, T) for j in range(R // T) for i in range(R // T)]
@@ -235,7 +124,7 @@ def test_mosaic_and_one_launch(qb3):
         qdev.profile_reset()
     assert got == 64, qb3.last_error()
     assert counts.get("dec_window") == 1, counts
-    assert paths(qb3, dec, 64) == [1] * 64
+    assert paths(qb3, dec.p, 64) == [1] * 64
     assert torch.equal(buf[:R * R * b].view(R, R * b), as_rows(img, Ht)[Y0:Y0 + R, X0 * b:(X0 + R) * b])
     assert bool((buf[R * R * b:] == SENTINEL).all())
     dec.close()
@@ -247,16 +136,16 @@ def test_quanta(qb3):
     from qb3_amd import device as qdev, synth
     Wd, Ht, b = 1000, 300, 3
     img = synth.generate(Wd, Ht, b, 0, "NOISY3", 11)
-    d_c, n = make_container(qb3, img, 0, BASE, 2, quanta=3)
+    d_c, n, _ = make_container(qb3, img, 0, BASE, 2, quanta=3)
     want, st = full_decode(qb3, d_c, n)
     assert want is not None and not torch.equal(want, img.reshape(-1))
     dec = qdev.DeviceDecoder(d_c, n)
     rects = W.windows(Wd, Ht, 3, 12)
-    lay = Layout(rects, b, 1)
+    lay = Layout(rects, b, 1, "u8")
     got, buf = batch_call(qb3, dec, d_c, lay)
     assert got == len(rects)
     lay.check(buf, want.view(Ht, -1))
-    assert paths(qb3, dec, len(rects)) == [1] * len(rects)
+    assert paths(qb3, dec.p, len(rects)) == [1] * len(rects)
     dec.close()
 
 
@@ -286,18 +175,18 @@ def test_merged_strips(qb3, case):
     Wd, Ht, b, dt, mode, gen = case
     tsz = qb3.TYPESIZE[dt]
     img = synth.generate(Wd, Ht, b, dt, gen, 19)
-    d_c, n = make_container(qb3, img, dt, mode, 2)
+    d_c, n, _ = make_container(qb3, img, dt, mode, 2)
     dec = qdev.DeviceDecoder(d_c, n)
     bps = C.c_size_t()
     L.qb3x_window_segments(dec.p, 0, 0, Wd, Ht, C.byref(bps))
     # without the whole raster and the large windows (they make the union trivial), and with them
     small = [r for r in W.windows(Wd, Ht, 23, 16, bps.value) if r[3] <= 40]
     for rects in (small, W.windows(Wd, Ht, 23, 16, bps.value)):
-        lay = Layout(rects, b * tsz, tsz)
+        lay = Layout(rects, b * tsz, tsz, "u8")
         got, buf = batch_call(qb3, dec, d_c, lay)
         assert got == len(rects), qb3.last_error()
         lay.check(buf, as_rows(img, Ht))
-        assert paths(qb3, dec, len(rects)) == [2] * len(rects)
+        assert paths(qb3, dec.p, len(rects)) == [2] * len(rects)
         assert L.qb3x_last_window_path(dec.p) == 2
         assert L.qb3x_last_window_segments(dec.p) == union_of_row_segments(Wd, Ht, rects, bps.value)
         assert L.qb3x_last_decode_status(dec.p) == 0
@@ -316,7 +205,7 @@ def check_path3_once(qb3, d_c, n, want_rows, Wd, Ht, pix, tsz, nwin=10, index=No
     L = qb3.lib
     st = _vp(torch.cuda.current_stream().cuda_stream)
     rects = W.windows(Wd, Ht, 41, nwin)
-    lay = Layout(rects, pix, tsz)
+    lay = Layout(rects, pix, tsz, "u8")
     qdev.profile_enable(1)
     try:
         qdev.profile_reset()
@@ -335,7 +224,7 @@ def check_path3_once(qb3, d_c, n, want_rows, Wd, Ht, pix, tsz, nwin=10, index=No
         qdev.profile_reset()
     assert got == len(rects), qb3.last_error()
     lay.check(buf, want_rows)
-    assert paths(qb3, dec, len(rects)) == [3] * len(rects) and L.qb3x_last_window_path(dec.p) == 3
+    assert paths(qb3, dec.p, len(rects)) == [3] * len(rects) and L.qb3x_last_window_path(dec.p) == 3
     for name in DECODE_KERNELS:
         assert many.get(name, 0) == one.get(name, 0), (name, one, many)
     assert "dec_window" not in many
@@ -348,7 +237,7 @@ def test_one_whole_decode_for_the_batch(qb3, oracle):
     import torch
     from qb3_amd import device as qdev, synth
     img = synth.generate(1000, 300, 3, 0, "NOISY3", 5)
-    d_c, n = make_container(qb3, img, 0, FTL, 1)
+    d_c, n, _ = make_container(qb3, img, 0, FTL, 1)
     check_path3_once(qb3, d_c, n, as_rows(img, 300), 1000, 300, 3, 1)
     enc = qdev.DeviceEncoder(1000, 300, 3, 0, mode=FTL, want_index=True, index_chunk=2)    # level 2, but the caller brings an index
     dst, n, index = enc.encode(img.reshape(-1))
@@ -374,34 +263,13 @@ def test_one_whole_decode_for_the_batch(qb3, oracle):
 
 
 # ---------------------------------------------------------------------------------------------------------------- trust
-def table_chunks(c):
-    """[(offset of an "ix" chunk, its length)] and the offset of the first stream byte"""
-    c = bytes(c[:200000]) if len(c) > 200000 else bytes(c)
-    pos, out = 11, []
-    while True:
-        sig, ln = c[pos:pos + 2], c[pos + 2] | c[pos + 3] << 8
-        if sig == b"DT":
-            return out, pos + 2
-        if sig == b"ix":
-            out.append((pos, ln))
-        pos += ln if sig in (b"ix", b"zz") else 4 + ln
-
-
-def chunk_check(entries):
-    """the 16-bit check of a version 3 table chunk: sum of (byte + 1) * (i * K + 1) mod 2^32, folded"""
-    e = np.frombuffer(bytes(entries), np.uint8).astype(np.uint64)
-    i = np.arange(len(e), dtype=np.uint64)
-    s = int((((e + 1) * ((i * 0x9e3779b1 + 1) & 0xffffffff)) & 0xffffffff).sum()) & 0xffffffff
-    return (s ^ (s >> 16)) & 0xffff
-
-
 def test_damage_costs_time_window_by_window(qb3):
     import torch
     from qb3_amd import device as qdev, synth
     L = qb3.lib
     Wd, Ht, b = 2048, 1024, 3
     img = synth.generate(Wd, Ht, b, 0, "NOISY3", 77)
-    d_c, n = make_container(qb3, img, 0, FTL, 2)
+    d_c, n, _ = make_container(qb3, img, 0, FTL, 2)
     host = d_c[:n].cpu().numpy()
     chunks, data_off = table_chunks(host)
     E = 6 + 2 * b + 80
@@ -422,7 +290,7 @@ def test_damage_costs_time_window_by_window(qb3):
         assert any((by * nbx + bx) // 64 == seg for by in range(r[1] // 4, (r[1] + r[3] - 1) // 4 + 1) for bx in range(r[0] // 4, (r[0] + r[2] - 1) // 4 + 1))
     for r in beside:
         assert not any((by * nbx + bx) // 64 == seg for by in range(r[1] // 4, (r[1] + r[3] - 1) // 4 + 1) for bx in range(r[0] // 4, (r[0] + r[2] - 1) // 4 + 1))
-    lay = Layout(rects, b, 1)
+    lay = Layout(rects, b, 1, "u8")
     e0 = chunks[0][0] + 12 + seg * E
 
     # a flipped byte in chunk 0, which only some windows read (the last two read the table's later chunks): the chunk fails its
@@ -437,7 +305,7 @@ def test_damage_costs_time_window_by_window(qb3):
         got, buf = batch_call(qb3, dec, bad, lay)
         assert got == len(rects), what
         lay.check(buf, ref.view(Ht, -1))
-        assert paths(qb3, dec, len(rects)) == [3] * len(rects), what
+        assert paths(qb3, dec.p, len(rects)) == [3] * len(rects), what
         assert L.qb3x_last_decode_status(dec.p) & 32, what
         dec.close()
 
@@ -457,7 +325,7 @@ def test_damage_costs_time_window_by_window(qb3):
     got, buf = batch_call(qb3, dec, bad, lay)
     assert got == len(rects)
     lay.check(buf, want)
-    assert paths(qb3, dec, len(rects)) == [3] * len(holds) + [1] * len(beside)
+    assert paths(qb3, dec.p, len(rects)) == [3] * len(holds) + [1] * len(beside)
     assert L.qb3x_last_window_path(dec.p) == 1
     assert L.qb3x_last_window_segments(dec.p) == sum(W.brute_segments(Wd, Ht, *r) for r in rects) + nseg
     dec.close()
@@ -472,12 +340,12 @@ def test_damage_costs_time_window_by_window(qb3):
     dec = qdev.DeviceDecoder(short, cut)
     got, buf = batch_call(qb3, dec, short, lay)
     if ref is None:
-        assert got == 0 and paths(qb3, dec, len(rects)) == [0] * len(rects)
+        assert got == 0 and paths(qb3, dec.p, len(rects)) == [0] * len(rects)
         lay.check(buf, None, skip=range(len(rects)))        # (a shortcut may have written windows before the whole decode failed)
     else:
         assert got == len(rects)
         lay.check(buf, ref.view(Ht, -1))
-        assert paths(qb3, dec, len(rects)) == [3] * len(rects)
+        assert paths(qb3, dec.p, len(rects)) == [3] * len(rects)
     dec.close()
 
 
@@ -491,13 +359,13 @@ def test_windows_of_a_container_in_host_memory(qb3, oracle):
     for (Wd, Ht, b, dt, mode, level, gen, path) in ((2051, 1030, 3, 0, BASE, 2, "NOISY3", 1), (1000, 520, 4, 2, FTL, 2, "LANDSAT16", 2), (1000, 300, 3, 0, FTL, 1, "NOISY3", 3)):
         tsz = qb3.TYPESIZE[dt]
         img = synth.generate(Wd, Ht, b, dt, gen, 3)
-        d_c, n = make_container(qb3, img, dt, mode, level)
+        d_c, n, _ = make_container(qb3, img, dt, mode, level)
         s = d_c[:n].cpu().numpy()
         rects = W.windows(Wd, Ht, 8, 12)
-        lay = Layout(rects, b * tsz, tsz)
+        lay = Layout(rects, b * tsz, tsz, "u8")
         dec = qdev.DeviceDecoder(d_c, n)
         got, dbuf = batch_call(qb3, dec, d_c, lay)
-        assert got == len(rects) and paths(qb3, dec, len(rects)) == [path] * len(rects)
+        assert got == len(rects) and paths(qb3, dec.p, len(rects)) == [path] * len(rects)
         dec.close()
         hbuf = np.full(lay.size, SENTINEL, np.uint8)
         strides = [0 if sb == r[2] * lay.pix else sb // tsz for sb, r in zip(lay.sbytes, rects)]
@@ -518,7 +386,7 @@ def test_python_interface(qb3):
     rects = [(13, 21, 101, 55), (0, 0, 1, 1), (250, 100, 33, 7), (13, 21, 101, 55)]
     for (w, h, b, dt, path) in ((700, 300, 3, 0, 1), (500, 260, 4, 2, 2), (300, 200, 1, 7, 2)):
         img = synth.generate(w, h, b, dt, "NOISY3", 8)
-        d_c, n = make_container(qb3, img, dt, FTL, 2)
+        d_c, n, _ = make_container(qb3, img, dt, FTL, 2)
         dec = qdev.DeviceDecoder(d_c, n)
         got = dec.decode_windows(d_c, rects)
         assert dec.last_windows == [path] * len(rects)
@@ -548,11 +416,11 @@ def test_a_batch_repeats(qb3):
     Wd, Ht, b = 2051, 1030, 3
     img = synth.generate(Wd, Ht, b, 0, "NOISY3", 2)
     rows = as_rows(img, Ht)
-    d_c, n = make_container(qb3, img, 0, BASE, 2)
+    d_c, n, _ = make_container(qb3, img, 0, BASE, 2)
     dec = qdev.DeviceDecoder(d_c, n)
     rects = W.windows(Wd, Ht, 6, 60)
-    lay = Layout(rects, b, 1)
-    small = Layout(rects[:3], b, 1)
+    lay = Layout(rects, b, 1, "u8")
+    small = Layout(rects[:3], b, 1, "u8")
     bufs = []
     for step in range(4):
         if step == 2:
@@ -563,7 +431,7 @@ def test_a_batch_repeats(qb3):
             small.check(sbuf, rows)
             continue
         got, buf = batch_call(qb3, dec, d_c, lay)
-        assert got == len(rects) and paths(qb3, dec, len(rects)) == [1] * len(rects)
+        assert got == len(rects) and paths(qb3, dec.p, len(rects)) == [1] * len(rects)
         lay.check(buf, rows)
         bufs.append(buf)
     assert torch.equal(bufs[0], bufs[1]) and torch.equal(bufs[0], bufs[2])

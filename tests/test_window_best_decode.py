@@ -7,7 +7,6 @@ With the bit set a call must go path 1, end with status 0 and count the window's
 give the same bytes by path 2.  The rasters (qb3_window_best.py) reach the index form, common-factor units with their own factor and
 with the one in force (across segment boundaries: the entry's), and the fast path beside them; test_window_best_plan.py shows on the CPU
 that every one of them is a coded common-factor container at every shape, band count and mode used here, so the mode byte is ASSERTED."""
-import ctypes as C
 import os
 import sys
 
@@ -18,97 +17,14 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import qb3_window as W  # noqa: E402
 import qb3_window16 as W16  # noqa: E402
 import qb3_window_best as WB  # noqa: E402
+from qb3_window_best import device_raster  # noqa: E402
+from qb3_window_dev import (FTL, SENTINEL, Layout, as_rows, batch_call, chunk_check, count, destination, full_decode,  # noqa: E402
+                            make_container, segments_of, single_calls, table_chunks, window_call)
 
 pytestmark = pytest.mark.gpu
 
-FTL = 8
 CF, CF_H, BEST = WB.CF, WB.CF_H, WB.BEST
 BIT = WB.QB3X_WINK_CF8
-SENTINEL = 0xc3
-_vp = C.c_void_p
-
-
-def make_container(qb3, img, dt, mode, level=2, cband=None, quanta=1, want_index=False):
-    """a container in device memory, written by this library from a device raster (h, w, bands) with qb3x_set_encoder_index_chunk
-    (p, level); returns (uint8 tensor with zeros behind the container, size, out-of-band index or None)"""
-    import torch
-    from qb3_amd import device as qdev
-    h, w, b = img.shape
-    enc = qdev.DeviceEncoder(w, h, b, dt, mode=mode, cband=cband, want_index=want_index, index_chunk=level)
-    if quanta > 1:
-        assert qb3.lib.qb3_set_encoder_quanta(enc.p, quanta, False)
-    dst, n, index = enc.encode(img.reshape(-1))
-    out = torch.zeros((n + 3) // 4 * 4 + 64, dtype=torch.uint8, device=img.device)
-    out[:n] = dst[:n]
-    index = index.clone() if index is not None else None
-    enc.close()
-    return out, n, index
-
-
-def device_raster(oracle, name, Wd, Ht, bands, seed):
-    import torch
-    return torch.from_numpy(WB.raster(oracle.generate, name, Wd, Ht, bands, seed)).cuda()
-
-
-def as_rows(t, h):
-    import torch
-    return t.contiguous().view(torch.uint8).reshape(h, -1)
-
-
-def full_decode(qb3, d_c, n):
-    """qb3x_decode_device on a handle of its own: the flat uint8 tensor, or None when the call fails"""
-    import torch
-    from qb3_amd import device as qdev
-    dec = qdev.DeviceDecoder(d_c, n)
-    out = torch.zeros(dec.out_bytes, dtype=torch.uint8, device=d_c.device)
-    got = qb3.lib.qb3x_decode_device(dec.p, _vp(d_c.data_ptr()), _vp(out.data_ptr()), None, _vp(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    dec.close()
-    return out if got else None
-
-
-def window_call(qb3, dec, d_c, win, want_rows, pix, k, index=None, tsz=1):
-    """one qb3x_decode_window_device into a sentinel-filled buffer.  k chooses the destination: it starts k % 4 bytes behind a dword
-    (behind 16 sentinel bytes) and its rows are tight (k % 3 == 0), a few values wider so that rows fall on every byte of a dword (1),
-    or whole dwords wider (2).  Checks payload and sentinels; want_rows None: the call is expected to fail.  Returns the bytes written"""
-    import torch
-    x0, y0, w, h = win
-    wline = w * pix
-    extra = (0, 1 + k % 7, 4 * (1 + k % 3))[k % 3]                 # values
-    sbytes = wline + tsz * extra
-    addr = 16 + tsz * (k % 4)
-    buf = torch.full((addr + (h + 1) * sbytes + 64,), SENTINEL, dtype=torch.uint8, device=d_c.device)
-    n = qb3.lib.qb3x_decode_window_device(dec.p, _vp(d_c.data_ptr()), _vp(index.data_ptr()) if index is not None else None, x0, y0, w, h,
-                                          _vp(buf.data_ptr() + addr), sbytes // tsz if extra else 0, _vp(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    rows = buf[addr:addr + h * sbytes].view(h, sbytes)
-    if want_rows is None:
-        rows[:, :wline] = SENTINEL
-        assert n == 0 and bool((buf == SENTINEL).all())
-        return 0
-    assert n == h * wline, (win, n, qb3.last_error())
-    want = want_rows[y0:y0 + h, x0 * pix:(x0 + w) * pix]
-    if not torch.equal(rows[:, :wline], want):
-        bad = (rows[:, :wline] != want).nonzero()
-        raise AssertionError("window %r (destination %d): %d bytes differ, the first at row %d byte %d" % (win, k, len(bad), int(bad[0][0]), int(bad[0][1])))
-    rows[:, :wline] = SENTINEL
-    assert bool((buf == SENTINEL).all()), "window %r (destination %d): bytes outside the window were written" % (win, k)
-    return n
-
-
-def count(qb3, name):
-    ms, cnt = C.c_double(), C.c_uint64()
-    return cnt.value if qb3.lib.qb3x_profile_get(name.encode(), C.byref(ms), C.byref(cnt)) else 0
-
-
-def segments_of(Wd, Ht, win, bps=64):
-    """the index segments that hold a block of the window (W.brute_segments' enumeration, as a set)"""
-    x0, y0, w, h = win
-    nbx, nby = W.blocks_of(Wd, Ht)
-    bx0, bx1 = min(x0 // 4, nbx - 1), min((x0 + w - 1) // 4, nbx - 1)
-    by0, by1 = min(y0 // 4, nby - 1), min((y0 + h - 1) // 4, nby - 1)
-    return {(by * nbx + bx) // bps for by in range(by0, by1 + 1) for bx in range(bx0, bx1 + 1)}
-
 
 CASES = [(b, s) for b in WB.BANDS for s in WB.SHAPES]
 
@@ -135,7 +51,7 @@ def test_window_best_kernel(qb3, oracle, case):
                     dec.set_window_kernels(BIT)
                     for win in W16.windows(Wd, Ht, 5 * Wd + bands + mode + level, 64, 6 if cband is None else 2):
                         k += 1
-                        window_call(qb3, dec, d_c, win, rows, bands, k)
+                        window_call(qb3, dec, d_c, win, rows, bands, 1, *destination("cf8", k, 1))
                         what = (name, mode, level, cband, win)
                         assert L.qb3x_last_window_path(dec.p) == 1 and L.qb3x_last_decode_status(dec.p) == 0, what
                         assert L.qb3x_last_window_segments(dec.p) == L.qb3x_window_segments(dec.p, *win, None) == W.brute_segments(Wd, Ht, *win), what
@@ -161,77 +77,17 @@ def test_the_bit_only_chooses_the_way(qb3, oracle, case):
         for i, win in enumerate(W16.windows(Wd, Ht, 17, 64, 6)):
             dec.set_window_kernels(BIT)
             before = count(qb3, "dec_window_best")
-            window_call(qb3, dec, d_c, win, rows, bands, i)
+            window_call(qb3, dec, d_c, win, rows, bands, 1, *destination("cf8", i, 1))
             assert L.qb3x_last_window_path(dec.p) == 1 and count(qb3, "dec_window_best") == before + 1, win
             assert L.qb3x_last_window_segments(dec.p) == W.brute_segments(Wd, Ht, *win), win
             dec.set_window_kernels(0)
-            window_call(qb3, dec, d_c, win, rows, bands, i)
+            window_call(qb3, dec, d_c, win, rows, bands, 1, *destination("cf8", i, 1))
             assert L.qb3x_last_window_path(dec.p) == 2 and count(qb3, "dec_window_best") == before + 1, win
             assert L.qb3x_last_window_segments(dec.p) == W.row_segments(Wd, Ht, win[1], win[3], 64), win
         assert count(qb3, "dec_window") == 0 and count(qb3, "dec_window16") == 0
     finally:
         L.qb3x_profile_enable(0)
     dec.close()
-
-
-class Layout:
-    """the destinations of a batch in one buffer: window k starts k % 4 bytes behind a dword, rows tight or wide"""
-
-    def __init__(self, rects, pix, mosaic=None):
-        self.rects, self.pix = rects, pix
-        self.offs, self.sbytes = [], []
-        if mosaic:                          # the windows side by side in rows of one image `mosaic` bytes wide: (column byte, row) each
-            for (col, row) in mosaic[1]:
-                self.offs.append(16 + row * mosaic[0] + col)
-                self.sbytes.append(mosaic[0])
-            self.size = 16 + mosaic[0] * mosaic[2] + 64
-            return
-        at = 16
-        for k, (x0, y0, w, h) in enumerate(rects):
-            at = (at + 3) // 4 * 4 + k % 4
-            sb = w * pix + (0, 1 + k % 7, 4 * (1 + k % 3))[k % 3]
-            self.offs.append(at)
-            self.sbytes.append(sb)
-            at += h * sb + 3
-        self.size = at + 64
-
-    def strides(self):
-        return [0 if sb == r[2] * self.pix else sb for sb, r in zip(self.sbytes, self.rects)]
-
-    def check(self, buf, want_rows):
-        import torch
-        buf = buf.clone()
-        for k, ((x0, y0, w, h), off, sb) in enumerate(zip(self.rects, self.offs, self.sbytes)):
-            rows = buf[off:off + h * sb].view(h, sb)
-            assert torch.equal(rows[:, :w * self.pix], want_rows[y0:y0 + h, x0 * self.pix:(x0 + w) * self.pix]), (k, self.rects[k])
-            rows[:, :w * self.pix] = SENTINEL
-        assert bool((buf == SENTINEL).all()), "bytes outside the windows were written"
-
-
-def batch_call(qb3, dec, d_c, lay, host=None):
-    """qb3x_decode_windows_device (host: qb3x_read_windows on that host handle) into a fresh sentinel buffer"""
-    import torch
-    if host is not None:
-        hbuf = np.full(lay.size, SENTINEL, np.uint8)
-        wins = qb3.window_array(lay.rects, [hbuf.ctypes.data + o for o in lay.offs], lay.strides())
-        n = qb3.lib.qb3x_read_windows(host, wins, len(lay.rects))
-        return n, torch.from_numpy(hbuf).cuda()
-    buf = torch.full((lay.size,), SENTINEL, dtype=torch.uint8, device="cuda")
-    wins = qb3.window_array(lay.rects, [buf.data_ptr() + o for o in lay.offs], lay.strides())
-    n = qb3.lib.qb3x_decode_windows_device(dec.p, _vp(d_c.data_ptr()), None, wins, len(lay.rects), _vp(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    return n, buf
-
-
-def single_calls(qb3, dec, d_c, lay):
-    """the layout's windows by n single calls into a fresh sentinel buffer"""
-    import torch
-    buf = torch.full((lay.size,), SENTINEL, dtype=torch.uint8, device="cuda")
-    for (x0, y0, w, h), off, stride in zip(lay.rects, lay.offs, lay.strides()):
-        assert qb3.lib.qb3x_decode_window_device(dec.p, _vp(d_c.data_ptr()), None, x0, y0, w, h, _vp(buf.data_ptr() + off), stride,
-                                                 _vp(torch.cuda.current_stream().cuda_stream)) == h * w * lay.pix
-    torch.cuda.synchronize()
-    return buf
 
 
 @pytest.mark.parametrize("case", ((3, 1001, 259, BEST, 2, "mixed"), (4, 260, 37, CF_H, 1, "scaled16"), (1, 100, 100, CF, 2, "PALETTE")),
@@ -257,7 +113,7 @@ def test_window_best_batch(qb3, oracle, case):
     try:
         for nwin in (1, 7, 200):
             rects = wins[5:5 + nwin] if nwin < 200 else wins[3:203]        # (random ones overlap each other and the fixed ones)
-            lay = Layout(rects, bands)
+            lay = Layout(rects, bands, 1, "cf8")
             total = sum(W.brute_segments(Wd, Ht, *r) for r in rects)
             before = count(qb3, "dec_window_best")
             got, buf = batch_call(qb3, dec, d_c, lay)
@@ -273,7 +129,7 @@ def test_window_best_batch(qb3, oracle, case):
     tw, th = min(40, Wd // 3), min(20, Ht // 2)
     rects = [((7 + 31 * i) % (Wd - tw), (5 + 13 * i) % (Ht - th), tw, th) for i in range(6)]
     line = 3 * tw * bands
-    lay = Layout(rects, bands, mosaic=(line, [((i % 3) * tw * bands, (i // 3) * th) for i in range(6)], 2 * th))
+    lay = Layout(rects, bands, 1, "cf8", mosaic=(line, [((i % 3) * tw * bands, (i // 3) * th) for i in range(6)], 2 * th))
     got, buf = batch_call(qb3, dec, d_c, lay)
     assert got == 6 and all(L.qb3x_window_path(dec.p, i) == 1 for i in range(6))
     mosaic = buf[16:16 + line * 2 * th].view(2 * th, -1)
@@ -290,31 +146,18 @@ def test_window_best_dequantises_the_window(qb3, oracle):
     Wd, Ht, b = 260, 37, 3
     img = device_raster(oracle, "mixed", Wd, Ht, b, 11)
     d_c, n, _ = make_container(qb3, img, 0, CF_H, 2, quanta=3)
-    want = full_decode(qb3, d_c, n)
+    want = full_decode(qb3, d_c, n)[0]
     assert want is not None and not torch.equal(want, img.reshape(-1))
     dec = qdev.DeviceDecoder(d_c, n)
     assert qb3.lib.qb3_get_mode(dec.p) == 5
     dec.set_window_kernels(BIT)
     for i, win in enumerate(W16.windows(Wd, Ht, 3, 64, 8)):
-        window_call(qb3, dec, d_c, win, want.view(Ht, -1), b, i)
+        window_call(qb3, dec, d_c, win, want.view(Ht, -1), b, 1, *destination("cf8", i, 1))
         assert qb3.lib.qb3x_last_window_path(dec.p) == 1
     dec.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------- trust
-def table_chunks(c):
-    """[(offset of an "ix" chunk, its length)] and the offset of the first stream byte"""
-    c = bytes(c)
-    pos, out = 11, []
-    while True:
-        sig, ln = c[pos:pos + 2], c[pos + 2] | c[pos + 3] << 8
-        if sig == b"DT":
-            return out, pos + 2
-        if sig == b"ix":
-            out.append((pos, ln))
-        pos += ln if sig in (b"ix", b"zz") else 4 + ln
-
-
 @pytest.mark.parametrize("bands", WB.BANDS)
 def test_damage_costs_time_not_pixels(qb3, oracle, bands):
     """a flipped entry bit under the old check (the chunk's check: status bit 5); a block's length, a block's entering rung and an
@@ -353,17 +196,17 @@ def test_damage_costs_time_not_pixels(qb3, oracle, bands):
         change(bad, entry_at(seg))
         assert not np.array_equal(bad, host)
         c0, cl = chunks[seg // per_chunk]
-        s16 = W16.seal(bad[c0 + 12:c0 + cl])
+        s16 = chunk_check(bad[c0 + 12:c0 + cl])
         bad[c0 + 6], bad[c0 + 7] = s16 & 255, s16 >> 8
         d_bad = torch.zeros_like(d_c)
         d_bad[:n] = torch.from_numpy(bad).cuda()
         return d_bad
 
     def expect_path3(bad, size, what, bit=0):
-        want = full_decode(qb3, bad, size)
+        want = full_decode(qb3, bad, size)[0]
         dec = qdev.DeviceDecoder(bad, size)
         dec.set_window_kernels(BIT)
-        window_call(qb3, dec, bad, win, None if want is None else want.view(Ht, -1), bands, 3)
+        window_call(qb3, dec, bad, win, None if want is None else want.view(Ht, -1), bands, 1, *destination("cf8", 3, 1))
         if want is not None:
             assert L.qb3x_last_window_path(dec.p) == 3 and L.qb3x_last_decode_status(dec.p) != 0, what
             assert L.qb3x_last_decode_status(dec.p) & bit == bit, what
@@ -371,11 +214,11 @@ def test_damage_costs_time_not_pixels(qb3, oracle, bands):
         return want
 
     c0, cl = chunks[seg // per_chunk]
-    assert W16.seal(host[c0 + 12:c0 + cl]) == int(host[c0 + 6]) | int(host[c0 + 7]) << 8      # (the formula is the encoder's)
+    assert chunk_check(host[c0 + 12:c0 + cl]) == int(host[c0 + 6]) | int(host[c0 + 7]) << 8      # (the formula is the encoder's)
     # the sound container first: path 1
     dec = qdev.DeviceDecoder(d_c, n)
     dec.set_window_kernels(BIT)
-    window_call(qb3, dec, d_c, win, rows, bands, 3)
+    window_call(qb3, dec, d_c, win, rows, bands, 1, *destination("cf8", 3, 1))
     assert L.qb3x_last_window_path(dec.p) == 1
     dec.close()
     # a flipped bit in the entry, the check left as it was
@@ -406,7 +249,7 @@ def test_damage_costs_time_not_pixels(qb3, oracle, bands):
     dec = qdev.DeviceDecoder(d_bad, n)
     dec.set_window_kernels(BIT)
     rects = [win] + W16.windows(Wd, Ht, 21, 64, 30)[1:]
-    lay = Layout(rects, bands)
+    lay = Layout(rects, bands, 1, "cf8")
     got, buf = batch_call(qb3, dec, d_bad, lay)
     assert got == len(rects), qb3.last_error()
     lay.check(buf, rows)
@@ -451,7 +294,7 @@ def test_host_flavour_and_python(qb3, oracle):
     assert L.qb3_get_mode(p) == 5
     L.qb3x_set_decoder_window_kernels(p, BIT)
     rects = W16.windows(Wd, Ht, 4, 64, 7)
-    lay = Layout(rects, b)
+    lay = Layout(rects, b, 1, "cf8")
     got, buf = batch_call(qb3, None, None, lay, host=p)
     assert got == len(rects), qb3.last_error()
     lay.check(buf, rows)
@@ -486,7 +329,7 @@ def test_not_taken_with_the_bit_set(qb3, oracle):
         assert L.qb3_get_mode(dec.p) == (mode if mode_byte is None else mode_byte)
         dec.set_window_kernels(mask)
         tsz = 1 if dt == 0 else 2
-        window_call(qb3, dec, d_c, win, as_rows(img, img.shape[0]), img.shape[2] * tsz, 1, index, tsz=tsz)
+        window_call(qb3, dec, d_c, win, as_rows(img, img.shape[0]), img.shape[2] * tsz, tsz, *destination("cf8", 1, tsz), index)
         assert L.qb3x_last_window_path(dec.p) == path, (dt, mode, img.shape)
         dec.close()
 

@@ -18,6 +18,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import qb3_window as W  # noqa: E402
 import qb3_window16 as W16  # noqa: E402
+import qb3_window_dev as D  # noqa: E402
 import qb3_window_unit as WU  # noqa: E402
 import qb3_window_best_unit as WBU  # noqa: E402
 
@@ -29,18 +30,13 @@ TSZ = WU.TSZ
 _vp = C.c_void_p
 
 
-def count(qb3, name):
-    ms, cnt = C.c_double(), C.c_uint64()
-    return cnt.value if qb3.lib.qb3x_profile_get(name.encode(), C.byref(ms), C.byref(cnt)) else 0
-
-
 def check_path1(qb3, dec, d_c, rows, Wd, Ht, pix, tsz, wins, k0=0):
     """every window with the bit set: path 1, status 0, the window's segments"""
     L = qb3.lib
-    bps = WU.segment_size(qb3, dec)
+    bps = D.segment_size(qb3, dec)
     dec.set_window_kernels(BIT)
     for i, win in enumerate(wins):
-        WU.window_call(qb3, dec, d_c, win, rows, pix, tsz, k0 + i)
+        D.window_call(qb3, dec, d_c, win, rows, pix, tsz, *D.destination("unit", k0 + i, tsz))
         assert L.qb3x_last_window_path(dec.p) == 1 and L.qb3x_last_decode_status(dec.p) == 0, win
         assert L.qb3x_last_window_segments(dec.p) == L.qb3x_window_segments(dec.p, *win, None) == W.brute_segments(Wd, Ht, *win, bps=bps), win
 
@@ -66,17 +62,17 @@ def test_window_best_unit_kernel(qb3, case):
             name, level = WBU.NAMES[g % 4], 2 - (g // 4 + mi) % 2
             g += 1
             img = WBU.device_raster(name, Wd, Ht, bands, dt, 31 * bands + Wd)
-            d_c, n, _ = WU.make_container(qb3, img, dt, mode, level, cband)
+            d_c, n, _ = D.make_container(qb3, img, dt, mode, level, cband)
             dec = qdev.DeviceDecoder(d_c, n)
             got_mode = qb3.lib.qb3_get_mode(dec.p)
             if (mode == BEST and got_mode == 7) or (name == "noisy" and got_mode == 255):      # the RLE0 pass won; noise that did not compress
                 dec.close()
                 continue
             assert got_mode == (CF_H if mode == BEST else mode), (name, mode, got_mode)
-            bps = WU.segment_size(qb3, dec)
+            bps = D.segment_size(qb3, dec)
             assert bps == WU.seg_blocks(bands)
-            rows = WU.as_rows(img, Ht)
-            whole = WU.full_decode(qb3, d_c, n)
+            rows = D.as_rows(img, Ht)
+            whole = D.full_decode(qb3, d_c, n)[0]
             assert whole is not None and torch.equal(whole.view(Ht, -1), rows)
             wins = W16.windows(Wd, Ht, 5 * Wd + bands + mode, bps, 12 if mi == 0 else 4)
             check_path1(qb3, dec, d_c, rows, Wd, Ht, pix, tsz, wins, g)
@@ -96,23 +92,23 @@ def test_window_best_unit_batch(qb3, case):
     dt, bands, Wd, Ht, mode, level, name = case
     tsz, pix = TSZ[dt], TSZ[dt] * bands
     img = WBU.device_raster(name, Wd, Ht, bands, dt, 77)
-    rows = WU.as_rows(img, Ht)
-    d_c, n, _ = WU.make_container(qb3, img, dt, mode, level)
+    rows = D.as_rows(img, Ht)
+    d_c, n, _ = D.make_container(qb3, img, dt, mode, level)
     dec = qdev.DeviceDecoder(d_c, n)
     assert L.qb3_get_mode(dec.p) == (CF_H if mode == BEST else mode)
-    bps = WU.segment_size(qb3, dec)
+    bps = D.segment_size(qb3, dec)
     wins = W16.windows(Wd, Ht, 9, bps, 65)
     host = d_c[:n].cpu().numpy() if dt in (WBU.I32, WBU.U8) else None
     dec.set_window_kernels(BIT)
     for nwin in (1, 2, 65):
         rects = wins[5:5 + nwin] if nwin < 65 else wins[3:68]          # (random ones overlap each other and the fixed ones)
-        lay = WU.Layout(rects, pix, tsz)
+        lay = D.Layout(rects, pix, tsz, "unit")
         total = sum(W.brute_segments(Wd, Ht, *r, bps=bps) for r in rects)
         L.qb3x_profile_enable(1)
         L.qb3x_profile_reset()
         try:
-            got, buf = WU.batch_call(qb3, dec, d_c, lay)
-            assert count(qb3, "dec_window_best_unit") == 1
+            got, buf = D.batch_call(qb3, dec, d_c, lay)
+            assert D.count(qb3, "dec_window_best_unit") == 1
         finally:
             L.qb3x_profile_enable(0)
         assert got == nwin, qb3.last_error()
@@ -122,24 +118,24 @@ def test_window_best_unit_batch(qb3, case):
         if host is not None and nwin != 2:
             p, _ = W.open_handle(L, host)
             L.qb3x_set_decoder_window_kernels(p, BIT)
-            got, buf = WU.batch_call(qb3, None, None, lay, host=p)
+            got, buf = D.batch_call(qb3, None, None, lay, host=p)
             assert got == nwin, qb3.last_error()
             lay.check(buf, rows)
             assert all(L.qb3x_window_path(p, i) == 1 for i in range(nwin)) and L.qb3x_last_window_segments(p) == total
-            out = np.full(7 * 9 * pix + 8, WU.SENTINEL, np.uint8)             # ... and the single host call
+            out = np.full(7 * 9 * pix + 8, D.SENTINEL, np.uint8)             # ... and the single host call
             assert L.qb3x_read_window(p, Wd - 9, Ht - 7, 9, 7, out.ctypes.data, 0) == 7 * 9 * pix and L.qb3x_last_window_path(p) == 1
-            assert np.array_equal(out[:7 * 9 * pix].reshape(7, -1), rows[Ht - 7:, (Wd - 9) * pix:].cpu().numpy()) and (out[7 * 9 * pix:] == WU.SENTINEL).all()
+            assert np.array_equal(out[:7 * 9 * pix].reshape(7, -1), rows[Ht - 7:, (Wd - 9) * pix:].cpu().numpy()) and (out[7 * 9 * pix:] == D.SENTINEL).all()
             L.qb3_destroy_decoder(p)
     # a mosaic: 3 x 2 tiles from six places of the raster, side by side in one image
     tw, th = min(40, Wd // 3), min(20, Ht // 2)
     rects = [((7 + 31 * i) % (Wd - tw), (5 + 13 * i) % (Ht - th), tw, th) for i in range(6)]
-    lay = WU.Layout(rects, pix, tsz, mosaic=(3 * tw * bands, [((i % 3) * tw * bands, (i // 3) * th) for i in range(6)], 2 * th))
-    got, buf = WU.batch_call(qb3, dec, d_c, lay)
+    lay = D.Layout(rects, pix, tsz, "unit", mosaic=(3 * tw * bands, [((i % 3) * tw * bands, (i // 3) * th) for i in range(6)], 2 * th))
+    got, buf = D.batch_call(qb3, dec, d_c, lay)
     assert got == 6 and all(L.qb3x_window_path(dec.p, i) == 1 for i in range(6))
     mosaic = buf[16:16 + tsz * 3 * tw * bands * 2 * th].view(2 * th, -1)
     for i, (x0, y0, w, h) in enumerate(rects):
         assert torch.equal(mosaic[(i // 3) * th:(i // 3 + 1) * th, (i % 3) * tw * pix:(i % 3 + 1) * tw * pix], rows[y0:y0 + h, x0 * pix:(x0 + w) * pix]), i
-    assert bool((buf[:16] == WU.SENTINEL).all()) and bool((buf[16 + mosaic.numel():] == WU.SENTINEL).all())
+    assert bool((buf[:16] == D.SENTINEL).all()) and bool((buf[16 + mosaic.numel():] == D.SENTINEL).all())
     dec.close()
 
 
@@ -153,17 +149,17 @@ def test_the_bit_only_chooses_the_way(qb3, case):
     dt, bands, Wd, Ht, mode, level, name = case
     tsz, pix = TSZ[dt], TSZ[dt] * bands
     img = WBU.device_raster(name, Wd, Ht, bands, dt, 3)
-    rows = WU.as_rows(img, Ht)
-    d_c, n, _ = WU.make_container(qb3, img, dt, mode, level)
+    rows = D.as_rows(img, Ht)
+    d_c, n, _ = D.make_container(qb3, img, dt, mode, level)
     dec = qdev.DeviceDecoder(d_c, n)
     assert L.qb3_get_mode(dec.p) == mode
-    bps = WU.segment_size(qb3, dec)
+    bps = D.segment_size(qb3, dec)
     for i, win in enumerate(W16.windows(Wd, Ht, 41, bps, 8)):
         dec.set_window_kernels(BIT)
-        WU.window_call(qb3, dec, d_c, win, rows, pix, tsz, i)
+        D.window_call(qb3, dec, d_c, win, rows, pix, tsz, *D.destination("unit", i, tsz))
         assert L.qb3x_last_window_path(dec.p) == 1 and L.qb3x_last_window_segments(dec.p) == W.brute_segments(Wd, Ht, *win, bps=bps), win
         dec.set_window_kernels(0)
-        WU.window_call(qb3, dec, d_c, win, rows, pix, tsz, i)
+        D.window_call(qb3, dec, d_c, win, rows, pix, tsz, *D.destination("unit", i, tsz))
         assert L.qb3x_last_window_path(dec.p) == 2 and L.qb3x_last_window_segments(dec.p) == W.row_segments(Wd, Ht, win[1], win[3], bps), win
     dec.close()
 
@@ -176,13 +172,13 @@ def test_window_best_unit_dequantises_the_window(qb3, case):
     dt, b = case
     Wd, Ht, tsz = 260, 37, TSZ[dt]
     img = WBU.device_raster("mixed", Wd, Ht, b, dt, 11)
-    d_c, n, _ = WU.make_container(qb3, img, dt, CF_H, 2, quanta=3)
-    want = WU.full_decode(qb3, d_c, n)
+    d_c, n, _ = D.make_container(qb3, img, dt, CF_H, 2, quanta=3)
+    want = D.full_decode(qb3, d_c, n)[0]
     assert want is not None and not torch.equal(want, img.reshape(-1).view(torch.uint8))
     dec = qdev.DeviceDecoder(d_c, n)
     dec.set_window_kernels(BIT)
     for i, win in enumerate(W16.windows(Wd, Ht, 3, WU.seg_blocks(b), 8)):
-        WU.window_call(qb3, dec, d_c, win, want.view(Ht, -1), tsz * b, tsz, i)
+        D.window_call(qb3, dec, d_c, win, want.view(Ht, -1), tsz * b, tsz, *D.destination("unit", i, tsz))
         assert qb3.lib.qb3x_last_window_path(dec.p) == 1
     dec.close()
 
@@ -201,14 +197,14 @@ def test_damage_costs_time_not_pixels(qb3, case):
     tsz, pix = TSZ[dt], TSZ[dt] * bands
     Wd, Ht = 1000, 260
     img = WBU.device_raster("mixed", Wd, Ht, bands, dt, 5)
-    rows = WU.as_rows(img, Ht)
-    d_c, n, _ = WU.make_container(qb3, img, dt, CF_H, 2)
+    rows = D.as_rows(img, Ht)
+    d_c, n, _ = D.make_container(qb3, img, dt, CF_H, 2)
     host = d_c[:n].cpu().numpy()
-    chunks, data_off = WU.table_chunks(host)
+    chunks, data_off = D.table_chunks(host)
     E = WBU.entry_bytes(bands, tsz)
     dec = qdev.DeviceDecoder(d_c, n)
     assert L.qb3_get_mode(dec.p) == CF_H
-    bps = WU.segment_size(qb3, dec)
+    bps = D.segment_size(qb3, dec)
     nbx, nby = W.blocks_of(Wd, Ht)
     nseg = (nbx * nby + bps - 1) // bps
     assert L.qb3x_decoder_table_entries(dec.p) == nseg and sum(ln - 12 for _, ln in chunks) == nseg * E
@@ -232,27 +228,27 @@ def test_damage_costs_time_not_pixels(qb3, case):
         change(bad, entry_at(seg) + WBU.field_at(bands, tsz, lane))
         assert not np.array_equal(bad, host)
         c0, cl = chunks[seg // per_chunk]
-        s16 = W16.seal(bad[c0 + 12:c0 + cl])
+        s16 = D.chunk_check(bad[c0 + 12:c0 + cl])
         bad[c0 + 6], bad[c0 + 7] = s16 & 255, s16 >> 8
         return upload(bad)
 
     def expect_path3(bad, size, what, bit=0, may_refuse=False):
-        want = WU.full_decode(qb3, bad, size)
+        want = D.full_decode(qb3, bad, size)[0]
         assert want is not None or may_refuse, what
         dec = qdev.DeviceDecoder(bad, size)
         dec.set_window_kernels(BIT)
-        WU.window_call(qb3, dec, bad, win, None if want is None else want.view(Ht, -1), pix, tsz, 3)
+        D.window_call(qb3, dec, bad, win, None if want is None else want.view(Ht, -1), pix, tsz, *D.destination("unit", 3, tsz))
         if want is not None:
             assert L.qb3x_last_window_path(dec.p) == 3 and L.qb3x_last_decode_status(dec.p) & bit == bit, what
         dec.close()
         return want
 
     c0, cl = chunks[seg // per_chunk]
-    assert W16.seal(host[c0 + 12:c0 + cl]) == int(host[c0 + 6]) | int(host[c0 + 7]) << 8      # (the formula is the encoder's)
+    assert D.chunk_check(host[c0 + 12:c0 + cl]) == int(host[c0 + 6]) | int(host[c0 + 7]) << 8      # (the formula is the encoder's)
     # the sound container first: path 1
     dec = qdev.DeviceDecoder(d_c, n)
     dec.set_window_kernels(BIT)
-    WU.window_call(qb3, dec, d_c, win, rows, pix, tsz, 3)
+    D.window_call(qb3, dec, d_c, win, rows, pix, tsz, *D.destination("unit", 3, tsz))
     assert L.qb3x_last_window_path(dec.p) == 1
     dec.close()
     # a flipped bit in a field, the check left as it was
@@ -295,11 +291,11 @@ def test_not_taken_with_the_bit_set(qb3, oracle):
     win = (13, 9, 101, 21)
 
     def one(img, dt, mode, level, path, want_index=False, addr=None, mode_byte=None):
-        d_c, n, index = WU.make_container(qb3, img, dt, mode, level, want_index=want_index)
+        d_c, n, index = D.make_container(qb3, img, dt, mode, level, want_index=want_index)
         dec = qdev.DeviceDecoder(d_c, n)
         assert L.qb3_get_mode(dec.p) == (mode if mode_byte is None else mode_byte)
         dec.set_window_kernels(BIT)
-        WU.window_call(qb3, dec, d_c, win, WU.as_rows(img, img.shape[0]), TSZ[dt] * img.shape[2], TSZ[dt], 0, index, addr=addr)
+        D.window_call(qb3, dec, d_c, win, D.as_rows(img, img.shape[0]), TSZ[dt] * img.shape[2], TSZ[dt], *D.destination("unit", 0, TSZ[dt], addr), index)
         assert L.qb3x_last_window_path(dec.p) == path, (dt, mode, level, addr)
         dec.close()
 
@@ -313,11 +309,11 @@ def test_not_taken_with_the_bit_set(qb3, oracle):
         one(torch.from_numpy(oracle.generate(260, 37, 5, 0, "CONST", 1)).cuda(), WBU.U8, BEST, 2, 3, mode_byte=7)
         one(WBU.device_raster("mixed", 260, 37, 2, WBU.I16, 1), WBU.I16, CF_H, 2, 2, addr=17)
         one(WBU.device_raster("scaled", 260, 37, 2, WBU.I64, 1), WBU.I64, CF, 2, 2, addr=20)
-        assert count(qb3, "dec_window_best_unit") == 0
+        assert D.count(qb3, "dec_window_best_unit") == 0
         one(WBU.device_raster("mixed", 260, 37, 5, WBU.U8, 1), WBU.U8, CF_H, 2, 1)
         one(WBU.device_raster("mixed", 260, 37, 2, WBU.I16, 1), WBU.I16, CF_H, 2, 1, addr=18)
         one(WBU.device_raster("scaled", 260, 37, 2, WBU.I64, 1), WBU.I64, CF, 2, 1, addr=24)
-        assert count(qb3, "dec_window_best_unit") == 3
+        assert D.count(qb3, "dec_window_best_unit") == 3
     finally:
         L.qb3x_profile_enable(0)
 
@@ -328,7 +324,7 @@ def test_a_ranged_handle_reads_the_container_whole_and_takes_the_kernel(qb3):
     import qb3_amd
     Wd, Ht, b = 201, 67, 3
     img = WBU.device_raster("mixed", Wd, Ht, b, WBU.U16, 3)
-    d_c, n, _ = WU.make_container(qb3, img, WBU.U16, CF_H, 2)
+    d_c, n, _ = D.make_container(qb3, img, WBU.U16, CF_H, 2)
     host = d_c[:n].cpu().numpy()
     src = WBU.raster("mixed", Wd, Ht, b, WBU.U16, 3)
     rects = W16.windows(Wd, Ht, 17, WU.seg_blocks(b), 6)
@@ -345,7 +341,7 @@ def test_python_decode_window(qb3):
     from qb3_amd import device as qdev
     Wd, Ht, b = 260, 37, 2
     img = WBU.device_raster("few", Wd, Ht, b, WBU.I32, 2)
-    d_c, n, _ = WU.make_container(qb3, img, WBU.I32, CF_H, 2)
+    d_c, n, _ = D.make_container(qb3, img, WBU.I32, CF_H, 2)
     dec = qdev.DeviceDecoder(d_c, n)
     dec.set_window_kernels(qb3.QB3X_WINK_CFU)
     one = dec.decode_window(d_c, 33, 5, 100, 20)

@@ -11,85 +11,11 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import qb3_window as W  # noqa: E402
+from qb3_window_dev import (FTL, BASE, BASE_Z, CF_H, RLE, ZCURVE, SENTINEL,  # noqa: E402
+                            as_rows, full_decode, make_container, table_chunks, to_device, window_call)
 
 pytestmark = pytest.mark.gpu
 
-FTL, BASE, BASE_Z, CF_H, RLE = 8, 4, 0, 5, 2
-ZCURVE = 0x0145236789cdabef
-SENTINEL = 0xc3
-_vp = C.c_void_p
-
-
-def make_container(qb3, img, dt, mode, level=2, cband=None, zorder=False, quanta=1):
-    """a container in device memory, written by this library from a device raster (h, w, bands); returns (uint8 tensor, size)"""
-    import torch
-    from qb3_amd import device as qdev
-    h, w, b = img.shape
-    enc = qdev.DeviceEncoder(w, h, b, dt, mode=mode, cband=cband, want_index=False, index_chunk=level)
-    if zorder:
-        qb3.lib.qb3_set_encoder_mode(enc.p, 0)          # the Z order sticks to the handle (reference QB3encode.cpp:124-132)
-    if quanta > 1:
-        assert qb3.lib.qb3_set_encoder_quanta(enc.p, quanta, False)
-    dst, n, _ = enc.encode(img.reshape(-1))
-    out = torch.zeros((n + 3) // 4 * 4 + 64, dtype=torch.uint8, device=img.device)
-    out[:n] = dst[:n]
-    enc.close()
-    return out, n
-
-
-def to_device(host, pad=64):
-    import torch
-    out = torch.zeros((len(host) + 3) // 4 * 4 + pad, dtype=torch.uint8, device="cuda")
-    out[:len(host)] = torch.from_numpy(np.ascontiguousarray(host))
-    return out
-
-
-def as_rows(t, h):
-    """a raster (device tensor of any type) as h rows of bytes"""
-    import torch
-    return t.contiguous().view(torch.uint8).reshape(h, -1)
-
-
-def window_call(qb3, dec, d_c, win, want_rows, pix, tsz, extra=0, addr=0, index=None):
-    """one qb3x_decode_window_device into a sentinel-filled buffer at byte offset `addr`, rows `extra` values apart beyond the
-    window's own; returns the byte count after checking payload and sentinel.  want_rows: the raster as rows of bytes, or None
-    when the call is expected to fail"""
-    import torch
-    L = qb3.lib
-    x0, y0, w, h = win
-    wline = w * pix
-    sbytes = wline + extra * tsz
-    buf = torch.full((addr + (h + 1) * sbytes + 64,), SENTINEL, dtype=torch.uint8, device=d_c.device)
-    n = L.qb3x_decode_window_device(dec.p, _vp(d_c.data_ptr()), _vp(index.data_ptr()) if index is not None else None, x0, y0, w, h,
-                                    _vp(buf.data_ptr() + addr), sbytes // tsz if extra else 0, _vp(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    rows = buf[addr:addr + h * sbytes].view(h, sbytes)
-    if want_rows is None:                               # (a shortcut may have written the window before the whole decode failed)
-        rows[:, :wline] = SENTINEL
-        assert n == 0 and bool((buf == SENTINEL).all())
-        return 0
-    assert n == h * wline, (win, n, qb3.last_error())
-    want = want_rows[y0:y0 + h, x0 * pix:(x0 + w) * pix]
-    if not torch.equal(rows[:, :wline], want):
-        bad = (rows[:, :wline] != want).nonzero()
-        raise AssertionError("window %r (stride +%d, address +%d): %d bytes differ, the first at row %d byte %d" %
-                             (win, extra, addr, len(bad), int(bad[0][0]), int(bad[0][1])))
-    rows[:, :wline] = SENTINEL
-    assert bool((buf == SENTINEL).all()), "window %r (stride +%d, address +%d): bytes outside the window were written" % (win, extra, addr)
-    return n
-
-
-def full_decode(qb3, d_c, n):
-    """qb3x_decode_device on a handle of its own: (flat uint8 tensor or None when the call fails, status)"""
-    import torch
-    from qb3_amd import device as qdev
-    dec = qdev.DeviceDecoder(d_c, n)
-    out = torch.zeros(dec.out_bytes, dtype=torch.uint8, device=d_c.device)
-    got = qb3.lib.qb3x_decode_device(dec.p, _vp(d_c.data_ptr()), _vp(out.data_ptr()), None, _vp(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    st = qb3.lib.qb3x_last_decode_status(dec.p)
-    dec.close()
-    return (out if got else None), st
 
 
 # ---------------------------------------------------------------------------------------------------------------- path 1
@@ -115,7 +41,7 @@ def test_window_kernel(qb3, shape, bands):
     cases = [(FTL, False), (BASE, False), (BASE_Z, False)] + ([(FTL, True)] if Wd % 4 == 0 and Ht % 4 == 0 else [])
     for mode, sticky_z in cases:
         for cband in maps:
-            d_c, n = make_container(qb3, img, 0, mode, 2, cband, sticky_z)
+            d_c, n, _ = make_container(qb3, img, 0, mode, 2, cband, zorder=sticky_z)
             dec = qdev.DeviceDecoder(d_c, n)
             assert L.qb3_get_mode(dec.p) == mode and (L.qb3_get_order(dec.p) == ZCURVE) == (mode == BASE_Z or sticky_z)
             want = rows
@@ -127,7 +53,7 @@ def test_window_kernel(qb3, shape, bands):
             for i, win in enumerate(wins):
                 for extra in (0, 1 + (i * 7) % 29):
                     k += 1
-                    window_call(qb3, dec, d_c, win, want, bands, 1, extra, k % 4)
+                    window_call(qb3, dec, d_c, win, want, bands, 1, k % 4, extra)
                     assert L.qb3x_last_window_path(dec.p) == 1, win
                     assert L.qb3x_last_window_segments(dec.p) == L.qb3x_window_segments(dec.p, *win, None) == W.brute_segments(Wd, Ht, *win)
                     assert L.qb3x_last_decode_status(dec.p) == 0
@@ -140,12 +66,12 @@ def test_window_kernel_dequantises_the_window(qb3):
     from qb3_amd import device as qdev, synth
     Wd, Ht, b = 1000, 300, 3
     img = synth.generate(Wd, Ht, b, 0, "NOISY3", 11)
-    d_c, n = make_container(qb3, img, 0, BASE, 2, quanta=3)
+    d_c, n, _ = make_container(qb3, img, 0, BASE, 2, quanta=3)
     want, st = full_decode(qb3, d_c, n)
     assert want is not None and not torch.equal(want, img.reshape(-1))     # lossy: the reference bytes are the whole decode's
     dec = qdev.DeviceDecoder(d_c, n)
     for i, win in enumerate(W.windows(Wd, Ht, 3, 12)):
-        window_call(qb3, dec, d_c, win, want.view(Ht, -1), b, 1, (0, 9)[i % 2], 0)
+        window_call(qb3, dec, d_c, win, want.view(Ht, -1), b, 1, 0, (0, 9)[i % 2])
         assert qb3.lib.qb3x_last_window_path(dec.p) == 1
     dec.close()
 
@@ -166,12 +92,12 @@ def test_strip_of_block_rows(qb3, case):
     tsz = qb3.TYPESIZE[dt]
     img = synth.generate(Wd, Ht, b, dt, gen, 19)
     rows = as_rows(img, Ht)
-    d_c, n = make_container(qb3, img, dt, mode, 2)
+    d_c, n, _ = make_container(qb3, img, dt, mode, 2)
     dec = qdev.DeviceDecoder(d_c, n)
     bps = C.c_size_t()
     L.qb3x_window_segments(dec.p, 0, 0, Wd, Ht, C.byref(bps))
     for i, win in enumerate(W.windows(Wd, Ht, 23, 16, bps.value)):
-        window_call(qb3, dec, d_c, win, rows, b * tsz, tsz, (0, 5)[i % 2], 0)
+        window_call(qb3, dec, d_c, win, rows, b * tsz, tsz, 0, (0, 5)[i % 2])
         assert L.qb3x_last_window_path(dec.p) == 2, win
         assert L.qb3x_last_window_segments(dec.p) == W.row_segments(Wd, Ht, win[1], win[3], bps.value)
         assert L.qb3x_last_decode_status(dec.p) == 0
@@ -183,7 +109,7 @@ def check_path3(qb3, d_c, n, want_rows, Wd, Ht, pix, tsz, nwin=10, index=None):
     from qb3_amd import device as qdev
     dec = qdev.DeviceDecoder(d_c, n)
     for i, win in enumerate(W.windows(Wd, Ht, 41, nwin)):
-        window_call(qb3, dec, d_c, win, want_rows, pix, tsz, (0, 3)[i % 2], 0, index)
+        window_call(qb3, dec, d_c, win, want_rows, pix, tsz, 0, (0, 3)[i % 2], index)
         assert qb3.lib.qb3x_last_window_path(dec.p) == 3, win
     dec.close()
 
@@ -195,7 +121,7 @@ def test_whole_decode_and_crop(qb3, oracle):
     from qb3_amd import device as qdev, synth
     L = qb3.lib
     img = synth.generate(1000, 300, 3, 0, "NOISY3", 5)
-    d_c, n = make_container(qb3, img, 0, FTL, 1)                            # level 1: positions and states, no block lengths
+    d_c, n, _ = make_container(qb3, img, 0, FTL, 1)                            # level 1: positions and states, no block lengths
     check_path3(qb3, d_c, n, as_rows(img, 300), 1000, 300, 3, 1)
     enc = qdev.DeviceEncoder(1000, 300, 3, 0, mode=FTL, want_index=True, index_chunk=2)    # level 2, but the caller brings an index
     dst, n, index = enc.encode(img.reshape(-1))
@@ -213,7 +139,7 @@ def test_whole_decode_and_crop(qb3, oracle):
         check_path3(qb3, to_device(s), len(s), torch.from_numpy(himg.view(np.uint8).reshape(h, -1)).cuda(), w, h, b * tsz, tsz)
     # this library's own RLE container keeps its level-2 table in front of the packed bytes: still the whole decode
     timg = torch.from_numpy(oracle.generate(600, 300, 3, 0, "TERRACE", 5)).cuda()
-    d_c, n = make_container(qb3, timg, 0, RLE, 2)
+    d_c, n, _ = make_container(qb3, timg, 0, RLE, 2)
     assert int(d_c[10]) == RLE
     check_path3(qb3, d_c, n, as_rows(timg, 300), 600, 300, 3, 1, 6)
     # quanta: lossy, the reference bytes are the whole decode's on a second handle
@@ -227,19 +153,6 @@ def test_whole_decode_and_crop(qb3, oracle):
 
 
 # ---------------------------------------------------------------------------------------------------------------- trust
-def table_chunks(c):
-    """[(offset of an "ix" chunk, its length)] and the offset of the first stream byte"""
-    c = bytes(c[:200000]) if len(c) > 200000 else bytes(c)
-    pos, out = 11, []
-    while True:
-        sig, ln = c[pos:pos + 2], c[pos + 2] | c[pos + 3] << 8
-        if sig == b"DT":
-            return out, pos + 2
-        if sig == b"ix":
-            out.append((pos, ln))
-        pos += ln if sig in (b"ix", b"zz") else 4 + ln
-
-
 def test_damaged_tables_and_short_streams_cost_time_not_pixels(qb3):
     import torch
     from qb3_amd import device as qdev, synth
@@ -247,7 +160,7 @@ def test_damaged_tables_and_short_streams_cost_time_not_pixels(qb3):
     Wd, Ht, b = 2048, 1024, 3
     img = synth.generate(Wd, Ht, b, 0, "NOISY3", 77)
     rows = as_rows(img, Ht)
-    d_c, n = make_container(qb3, img, 0, FTL, 2)
+    d_c, n, _ = make_container(qb3, img, 0, FTL, 2)
     host = d_c[:n].cpu().numpy()
     chunks, data_off = table_chunks(host)
     E = 6 + 2 * b + 80
@@ -265,7 +178,7 @@ def test_damaged_tables_and_short_streams_cost_time_not_pixels(qb3):
         bad[at] ^= 0x10
         dec = qdev.DeviceDecoder(bad, n)
         assert L.qb3x_decoder_table_entries(dec.p) == nseg, what
-        window_call(qb3, dec, bad, win, rows, b, 1, 4, 1)
+        window_call(qb3, dec, bad, win, rows, b, 1, 1, 4)
         if what != "unused chunk":
             assert L.qb3x_last_window_path(dec.p) == 3, what
             assert L.qb3x_last_decode_status(dec.p) & 32, what
@@ -295,7 +208,7 @@ def test_window_of_a_container_in_host_memory(qb3, case):
     L = qb3.lib
     Wd, Ht, b, mode = case
     img = synth.generate(Wd, Ht, b, 0, "NOISY3", 3)
-    d_c, n = make_container(qb3, img, 0, mode, 2)
+    d_c, n, _ = make_container(qb3, img, 0, mode, 2)
     s = d_c[:n].cpu().numpy()
     himg = img.cpu().numpy()
     del d_c, img
@@ -321,7 +234,7 @@ def test_python_interface(qb3):
     from qb3_amd import device as qdev, synth
     for (w, h, b, dt, path) in ((700, 300, 3, 0, 1), (500, 260, 4, 2, 2), (300, 200, 1, 7, 2)):
         img = synth.generate(w, h, b, dt, "NOISY3", 8)
-        d_c, n = make_container(qb3, img, dt, FTL, 2)
+        d_c, n, _ = make_container(qb3, img, dt, FTL, 2)
         dec = qdev.DeviceDecoder(d_c, n)
         got = dec.decode_window(d_c, 13, 21, 101, 55)
         assert got.shape == (55, 101, b) and got.element_size() == qb3.TYPESIZE[dt] and str(got.dtype) == "torch." + qb3.NP_DTYPE[dt]
@@ -342,14 +255,14 @@ def test_a_window_repeats(qb3):
     Wd, Ht, b = 2051, 1030, 3
     img = synth.generate(Wd, Ht, b, 0, "NOISY3", 2)
     rows = as_rows(img, Ht)
-    d_c, n = make_container(qb3, img, 0, BASE, 2)
+    d_c, n, _ = make_container(qb3, img, 0, BASE, 2)
     win = (1001, 517, 600, 300)
     dec = qdev.DeviceDecoder(d_c, n)
     for _ in range(3):
         window_call(qb3, dec, d_c, win, rows, b, 1, 0, 0)
         assert qb3.lib.qb3x_last_window_path(dec.p) == 1
     dec.close()
-    d_c2, n2 = make_container(qb3, img, 0, BASE, 2)     # an encode has just used LDS and registers
+    d_c2, n2, _ = make_container(qb3, img, 0, BASE, 2)     # an encode has just used LDS and registers
     dec = qdev.DeviceDecoder(d_c2, n2)
     window_call(qb3, dec, d_c2, win, rows, b, 1, 0, 0)
     assert qb3.lib.qb3x_last_window_path(dec.p) == 1 and n2 == n and torch.equal(d_c2[:n], d_c[:n])

@@ -18,6 +18,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import qb3_window as W  # noqa: E402
 import qb3_window16 as W16  # noqa: E402
+import qb3_window_dev as D  # noqa: E402
 import qb3_window_unit as WU  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -31,14 +32,14 @@ _vp = C.c_void_p
 def check_windows(qb3, dec, d_c, rows, Wd, Ht, pix, tsz, wins, k0=0):
     """every window with the bit set (path 1, status 0, the window's segments) and with the mask back at 0 (path 2, the rows')"""
     L = qb3.lib
-    bps = WU.segment_size(qb3, dec)
+    bps = D.segment_size(qb3, dec)
     for i, win in enumerate(wins):
         dec.set_window_kernels(BIT)
-        WU.window_call(qb3, dec, d_c, win, rows, pix, tsz, k0 + i)
+        D.window_call(qb3, dec, d_c, win, rows, pix, tsz, *D.destination("unit", k0 + i, tsz))
         assert L.qb3x_last_window_path(dec.p) == 1 and L.qb3x_last_decode_status(dec.p) == 0, win
         assert L.qb3x_last_window_segments(dec.p) == L.qb3x_window_segments(dec.p, *win, None) == W.brute_segments(Wd, Ht, *win, bps=bps), win
         dec.set_window_kernels(0)
-        WU.window_call(qb3, dec, d_c, win, rows, pix, tsz, k0 + i)
+        D.window_call(qb3, dec, d_c, win, rows, pix, tsz, *D.destination("unit", k0 + i, tsz))
         assert L.qb3x_last_window_path(dec.p) == 2, win
         assert L.qb3x_last_window_segments(dec.p) == W.row_segments(Wd, Ht, win[1], win[3], bps), win
 
@@ -63,22 +64,22 @@ def test_window_unit_kernel(qb3, case):
             gen = WU.GENERATORS[g % 3]
             g += 1
             img = synth.generate(Wd, Ht, bands, dt, gen, 31 * bands + Wd)
-            d_c, n, _ = WU.make_container(qb3, img, dt, mode, 2, cband)
+            d_c, n, _ = D.make_container(qb3, img, dt, mode, 2, cband)
             dec = qdev.DeviceDecoder(d_c, n)
             if qb3.lib.qb3_get_mode(dec.p) == 255:          # STORED: the raster did not compress
                 dec.close()
                 continue
             assert qb3.lib.qb3_get_mode(dec.p) == mode
-            bps = WU.segment_size(qb3, dec)
+            bps = D.segment_size(qb3, dec)
             assert bps == WU.seg_blocks(bands)
             wins = W16.windows(Wd, Ht, 5 * Wd + bands + mode, bps, 24 if mi == 0 else 8)
             if (dt, bands, Wd) == (WU.U8, 5, 1001):         # the whole raster (wins[0]): its first and last segment lie in different chunks
-                chunks, _ = WU.table_chunks(d_c[:n].cpu().numpy())
+                chunks, _ = D.table_chunks(d_c[:n].cpu().numpy())
                 E = WU.entry_bytes(bands, tsz)
                 nseg = W.brute_segments(Wd, Ht, 0, 0, Wd, Ht, bps=bps)
                 assert len(chunks) >= 2 and sum(ln - 12 for _, ln in chunks) == nseg * E and wins[0] == (0, 0, Wd, Ht)
                 assert (nseg - 1) // ((chunks[0][1] - 12) // E) >= 1
-            check_windows(qb3, dec, d_c, WU.as_rows(img, Ht), Wd, Ht, pix, tsz, wins, g)
+            check_windows(qb3, dec, d_c, D.as_rows(img, Ht), Wd, Ht, pix, tsz, wins, g)
             decoded += 1
             dec.close()
     assert decoded >= 1, "every container of the case came out STORED"
@@ -95,50 +96,50 @@ def test_window_unit_batch(qb3, case):
     dt, bands, Wd, Ht, mode, gen = case
     tsz, pix = TSZ[dt], TSZ[dt] * bands
     img = synth.generate(Wd, Ht, bands, dt, gen, 77)
-    rows = WU.as_rows(img, Ht)
-    d_c, n, _ = WU.make_container(qb3, img, dt, mode, 2)
+    rows = D.as_rows(img, Ht)
+    d_c, n, _ = D.make_container(qb3, img, dt, mode, 2)
     dec = qdev.DeviceDecoder(d_c, n)
     assert L.qb3_get_mode(dec.p) == mode
-    bps = WU.segment_size(qb3, dec)
+    bps = D.segment_size(qb3, dec)
     wins = W16.windows(Wd, Ht, 9, bps, 65)
     host = d_c[:n].cpu().numpy() if dt in (WU.I32, WU.U8) else None
     for nwin in (1, 2, 65):
         rects = wins[5:5 + nwin] if nwin < 65 else wins[3:68]          # (random ones overlap each other and the fixed ones)
-        lay = WU.Layout(rects, pix, tsz)
+        lay = D.Layout(rects, pix, tsz, "unit")
         total = sum(W.brute_segments(Wd, Ht, *r, bps=bps) for r in rects)
         dec.set_window_kernels(BIT)
-        got, buf = WU.batch_call(qb3, dec, d_c, lay)
+        got, buf = D.batch_call(qb3, dec, d_c, lay)
         assert got == nwin, qb3.last_error()
         lay.check(buf, rows)
         assert all(L.qb3x_window_ok(dec.p, i) == 1 and L.qb3x_window_path(dec.p, i) == 1 for i in range(nwin))
         assert L.qb3x_last_window_segments(dec.p) == total and L.qb3x_last_decode_status(dec.p) == 0
         dec.set_window_kernels(0)
-        got, buf = WU.batch_call(qb3, dec, d_c, lay)
+        got, buf = D.batch_call(qb3, dec, d_c, lay)
         assert got == nwin
         lay.check(buf, rows)
         assert all(L.qb3x_window_path(dec.p, i) == 2 for i in range(nwin))
         if host is not None and nwin != 2:
             p, _ = W.open_handle(L, host)
             L.qb3x_set_decoder_window_kernels(p, BIT)
-            got, buf = WU.batch_call(qb3, None, None, lay, host=p)
+            got, buf = D.batch_call(qb3, None, None, lay, host=p)
             assert got == nwin, qb3.last_error()
             lay.check(buf, rows)
             assert all(L.qb3x_window_path(p, i) == 1 for i in range(nwin)) and L.qb3x_last_window_segments(p) == total
-            out = np.full(7 * 9 * pix + 8, WU.SENTINEL, np.uint8)             # ... and the single host call
+            out = np.full(7 * 9 * pix + 8, D.SENTINEL, np.uint8)             # ... and the single host call
             assert L.qb3x_read_window(p, Wd - 9, Ht - 7, 9, 7, out.ctypes.data, 0) == 7 * 9 * pix and L.qb3x_last_window_path(p) == 1
-            assert np.array_equal(out[:7 * 9 * pix].reshape(7, -1), rows[Ht - 7:, (Wd - 9) * pix:].cpu().numpy()) and (out[7 * 9 * pix:] == WU.SENTINEL).all()
+            assert np.array_equal(out[:7 * 9 * pix].reshape(7, -1), rows[Ht - 7:, (Wd - 9) * pix:].cpu().numpy()) and (out[7 * 9 * pix:] == D.SENTINEL).all()
             L.qb3_destroy_decoder(p)
     # a mosaic: 3 x 2 tiles of 40 x 20 pixels from six places of the raster, side by side in one image of 120 x 40 pixels
     tw, th = min(40, Wd // 3), min(20, Ht // 2)
     rects = [((7 + 31 * i) % (Wd - tw), (5 + 13 * i) % (Ht - th), tw, th) for i in range(6)]
-    lay = WU.Layout(rects, pix, tsz, mosaic=(3 * tw * bands, [((i % 3) * tw * bands, (i // 3) * th) for i in range(6)], 2 * th))
+    lay = D.Layout(rects, pix, tsz, "unit", mosaic=(3 * tw * bands, [((i % 3) * tw * bands, (i // 3) * th) for i in range(6)], 2 * th))
     dec.set_window_kernels(BIT)
-    got, buf = WU.batch_call(qb3, dec, d_c, lay)
+    got, buf = D.batch_call(qb3, dec, d_c, lay)
     assert got == 6 and all(L.qb3x_window_path(dec.p, i) == 1 for i in range(6))
     mosaic = buf[16:16 + tsz * 3 * tw * bands * 2 * th].view(2 * th, -1)
     for i, (x0, y0, w, h) in enumerate(rects):
         assert torch.equal(mosaic[(i // 3) * th:(i // 3 + 1) * th, (i % 3) * tw * pix:(i % 3 + 1) * tw * pix], rows[y0:y0 + h, x0 * pix:(x0 + w) * pix]), i
-    assert bool((buf[:16] == WU.SENTINEL).all()) and bool((buf[16 + mosaic.numel():] == WU.SENTINEL).all())
+    assert bool((buf[:16] == D.SENTINEL).all()) and bool((buf[16 + mosaic.numel():] == D.SENTINEL).all())
     dec.close()
 
 
@@ -150,13 +151,13 @@ def test_window_unit_dequantises_the_window(qb3, case):
     dt, b = case
     Wd, Ht, tsz = 260, 37, TSZ[dt]
     img = synth.generate(Wd, Ht, b, dt, "NOISY3", 11)
-    d_c, n, _ = WU.make_container(qb3, img, dt, BASE, 2, quanta=3)
-    want = WU.full_decode(qb3, d_c, n)
+    d_c, n, _ = D.make_container(qb3, img, dt, BASE, 2, quanta=3)
+    want = D.full_decode(qb3, d_c, n)[0]
     assert want is not None and not torch.equal(want, img.reshape(-1).view(torch.uint8))
     dec = qdev.DeviceDecoder(d_c, n)
     dec.set_window_kernels(BIT)
     for i, win in enumerate(W16.windows(Wd, Ht, 3, WU.seg_blocks(b), 8)):
-        WU.window_call(qb3, dec, d_c, win, want.view(Ht, -1), tsz * b, tsz, i)
+        D.window_call(qb3, dec, d_c, win, want.view(Ht, -1), tsz * b, tsz, *D.destination("unit", i, tsz))
         assert qb3.lib.qb3x_last_window_path(dec.p) == 1
     dec.close()
 
@@ -175,13 +176,13 @@ def test_damaged_tables_and_short_streams_cost_time_not_pixels(qb3, case):
     tsz, pix = TSZ[dt], TSZ[dt] * bands
     Wd, Ht = 1001, 259
     img = synth.generate(Wd, Ht, bands, dt, "DEM", 5)
-    rows = WU.as_rows(img, Ht)
-    d_c, n, _ = WU.make_container(qb3, img, dt, FTL, 2)
+    rows = D.as_rows(img, Ht)
+    d_c, n, _ = D.make_container(qb3, img, dt, FTL, 2)
     host = d_c[:n].cpu().numpy()
-    chunks, data_off = WU.table_chunks(host)
+    chunks, data_off = D.table_chunks(host)
     E = WU.entry_bytes(bands, tsz)
     dec = qdev.DeviceDecoder(d_c, n)
-    bps = WU.segment_size(qb3, dec)
+    bps = D.segment_size(qb3, dec)
     nbx, nby = W.blocks_of(Wd, Ht)
     nseg = (nbx * nby + bps - 1) // bps
     assert L.qb3x_decoder_table_entries(dec.p) == nseg and sum(ln - 12 for _, ln in chunks) == nseg * E
@@ -200,10 +201,10 @@ def test_damaged_tables_and_short_streams_cost_time_not_pixels(qb3, case):
         return t
 
     def expect_path3(bad, size, what):
-        want = WU.full_decode(qb3, bad, size)
+        want = D.full_decode(qb3, bad, size)[0]
         dec = qdev.DeviceDecoder(bad, size)
         dec.set_window_kernels(BIT)
-        WU.window_call(qb3, dec, bad, win, None if want is None else want.view(Ht, -1), pix, tsz, 3)
+        D.window_call(qb3, dec, bad, win, None if want is None else want.view(Ht, -1), pix, tsz, *D.destination("unit", 3, tsz))
         if want is not None:
             assert L.qb3x_last_window_path(dec.p) == 3, what
         dec.close()
@@ -212,7 +213,7 @@ def test_damaged_tables_and_short_streams_cost_time_not_pixels(qb3, case):
     # the sound container first: path 1
     dec = qdev.DeviceDecoder(d_c, n)
     dec.set_window_kernels(BIT)
-    WU.window_call(qb3, dec, d_c, win, rows, pix, tsz, 3)
+    D.window_call(qb3, dec, d_c, win, rows, pix, tsz, *D.destination("unit", 3, tsz))
     assert L.qb3x_last_window_path(dec.p) == 1
     dec.close()
     e0 = entry_at(seg)
@@ -230,8 +231,8 @@ def test_damaged_tables_and_short_streams_cost_time_not_pixels(qb3, case):
     v = (v & ~(4095 << bit)) | (((f + 1) & 4095) << bit)
     bad[fields:fields + nf] = np.frombuffer(v.to_bytes(nf, "little"), np.uint8)
     c0, cl = chunks[seg // per_chunk]
-    s16 = W16.seal(bad[c0 + 12:c0 + cl])
-    assert W16.seal(host[c0 + 12:c0 + cl]) == int(host[c0 + 6]) | int(host[c0 + 7]) << 8      # (the formula is the encoder's)
+    s16 = D.chunk_check(bad[c0 + 12:c0 + cl])
+    assert D.chunk_check(host[c0 + 12:c0 + cl]) == int(host[c0 + 6]) | int(host[c0 + 7]) << 8      # (the formula is the encoder's)
     bad[c0 + 6], bad[c0 + 7] = s16 & 255, s16 >> 8
     want = expect_path3(upload(bad), n, "lengths")
     assert want is not None and torch.equal(want.view(Ht, -1), rows)
@@ -253,24 +254,20 @@ def test_not_taken_with_the_bit_set(qb3):
     win = (13, 9, 101, 21)
 
     def one(img, dt, mode, level, path, want_index=False, addr=None):
-        d_c, n, index = WU.make_container(qb3, img, dt, mode, level, want_index=want_index)
+        d_c, n, index = D.make_container(qb3, img, dt, mode, level, want_index=want_index)
         dec = qdev.DeviceDecoder(d_c, n)
         dec.set_window_kernels(BIT)
-        WU.window_call(qb3, dec, d_c, win, WU.as_rows(img, img.shape[0]), TSZ[dt] * img.shape[2], TSZ[dt], 0, index, addr=addr)
+        D.window_call(qb3, dec, d_c, win, D.as_rows(img, img.shape[0]), TSZ[dt] * img.shape[2], TSZ[dt], *D.destination("unit", 0, TSZ[dt], addr), index)
         assert L.qb3x_last_window_path(dec.p) == path, (dt, mode, level, addr)
         dec.close()
-
-    def count(name):
-        ms, cnt = C.c_double(), C.c_uint64()
-        return cnt.value if L.qb3x_profile_get(name.encode(), C.byref(ms), C.byref(cnt)) else 0
 
     L.qb3x_profile_enable(1)
     L.qb3x_profile_reset()
     try:
         one(synth.generate(260, 37, 3, WU.U8, "NOISY3", 1), WU.U8, FTL, 2, 1)
-        assert count("dec_window") == 1 and count("dec_window_unit") == 0
+        assert D.count(qb3, "dec_window") == 1 and D.count(qb3, "dec_window_unit") == 0
         one(synth.generate(260, 37, 5, WU.U8, "NOISY3", 1), WU.U8, FTL, 2, 1)
-        assert count("dec_window") == 1 and count("dec_window_unit") == 1
+        assert D.count(qb3, "dec_window") == 1 and D.count(qb3, "dec_window_unit") == 1
     finally:
         L.qb3x_profile_enable(0)
     one(synth.generate(260, 37, 4, WU.U16, "LANDSAT16", 1), WU.U16, FTL, 2, 2)
@@ -290,7 +287,7 @@ def test_a_ranged_handle_reads_the_container_whole_and_takes_the_kernel(qb3):
     from qb3_amd import synth
     Wd, Ht, b = 201, 67, 5
     img = synth.generate(Wd, Ht, b, WU.U8, "NOISY3", 3)
-    d_c, n, _ = WU.make_container(qb3, img, WU.U8, BASE, 2)
+    d_c, n, _ = D.make_container(qb3, img, WU.U8, BASE, 2)
     host = d_c[:n].cpu().numpy()
     src = img.cpu().numpy()
     rects = W16.windows(Wd, Ht, 17, WU.seg_blocks(b), 6)
