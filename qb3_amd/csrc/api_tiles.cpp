@@ -68,7 +68,9 @@ size_t qb3api::encode_tile_grids(encsp p, const TileGrid *grids, size_t ngrids, 
     uint8_t hdrbuf[80];
     size_t hdr = write_headers(p, hdrbuf);
     Geometry g = make_geometry(p->xsize, p->ysize, p->nbands, p->type, 0, p->order, p->mode, p->cband, nullptr);
-    EncPlan plan = plan_encode(g);          // (no function of the stride: one plan for every grid)
+    uintptr_t low = 0;                      // a tile of any grid off the alignment of its values: the plan of the kernels that read it
+    for (size_t gi = 0; gi < ngrids; gi++) low |= (uintptr_t)grids[gi].img | grids[gi].img_col | grids[gi].img_row;
+    EncPlan plan = plan_encode(g, (low & (tsz - 1)) == 0);      // (no function of the stride: one plan for every grid)
     size_t wsp = (plan.ws_bytes + 255) & ~(size_t)255;
     size_t batch = (size_t)8 << 30 >= wsp ? ((size_t)8 << 30) / wsp : 1;     // keep the workspace under 8 GiB
     if (batch > nmax) batch = nmax;

@@ -294,14 +294,14 @@ static bool pxw_eligible(const Geometry &g, bool best = false) {
     return (g.tsz >= 4 || (best && g.tsz == 2)) && g.bands == 1 && (g.mode == CM_BEST) == best && g.w >= 4 && g.h >= 4 && (g.order == HILBERT || g.order == ZCURVE) && !tuning().no_px;
 }
 
-EncPlan plan_encode(const Geometry &g) {
+EncPlan plan_encode(const Geometry &g, bool value_aligned) {
     EncPlan p;
     const uint32_t dpr = g.bands * g.tsz;
     p.px = px_eligible(g, &p.px_rgb);
     p.px16 = false; p.px16_bg = p.px16_ng = 0;
     p.pxw = false;
-    p.pxw_best = !p.px && pxw_eligible(g, true);        // (same chunks as the generic plan below: one band, slots = threads)
-    if (!p.px && pxw_eligible(g)) {
+    p.pxw_best = !p.px && value_aligned && pxw_eligible(g, true);        // (same chunks as the generic plan below: one band, slots = threads)
+    if (!p.px && value_aligned && pxw_eligible(g)) {
         p.pxw = true;
         p.threads = g.tsz == 8 ? 128 : 256; p.slots = p.threads; p.nbp = p.threads - 1;
         p.nchunks = (uint32_t)((g.nblocks + p.nbp - 1) / p.nbp);
@@ -319,7 +319,7 @@ EncPlan plan_encode(const Geometry &g) {
         return p;
     }
     bool rgb16 = false;
-    if (px16_eligible(g, &rgb16, &p.px16_bg, &p.px16_ng)) {
+    if (value_aligned && px16_eligible(g, &rgb16, &p.px16_bg, &p.px16_ng)) {
         p.px16 = true; p.px_rgb = rgb16;
         p.threads = 256; p.slots = 256 / p.px16_ng; p.nbp = p.slots - 1;
         p.nchunks = (uint32_t)((g.nblocks + p.nbp - 1) / p.nbp);

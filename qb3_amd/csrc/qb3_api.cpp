@@ -165,7 +165,7 @@ static size_t stored_encode_host(encsp p, const void *source, void *destination)
 static bool encode_blocks_device(encsp p, const Geometry &g, const void *d_img, uint8_t *d_out, size_t hdr,
                                  void *d_index, hipStream_t st, bool carry, uint64_t *bits, const uint8_t *hdrbytes,
                                  size_t hdr_stamp, const IxTable &ix, int *zero_run = nullptr) {
-    EncPlan plan = plan_encode(g);
+    EncPlan plan = plan_encode(g, ((uintptr_t)d_img & (g.tsz - 1)) == 0);
     if (!p->d_ws.ensure(plan.ws_bytes)) return false;
     BandState bs;
     memset(&bs, 0, sizeof(bs));

@@ -128,7 +128,10 @@ struct EncPlan {
     bool pxw;               // 32/64-bit single-band register-resident kernel applies (lane per block; k_enc_pxw.hip)
     bool pxw_best;          // ... its front end under the common-factor analysis (k_enc_best.hip, FRONT = 1 / 2)
 };
-EncPlan plan_encode(const Geometry &g);
+// value_aligned: the source pointer and the pitches between tiles are multiples of the value size.  Where they are not, the 16-bit and
+// one-band 32/64-bit lane-per-block kernels cannot read the raster and the plan is the unit-per-lane kernels' own -- their chunks, their
+// LDS -- not a lane-per-block plan handed to another kernel at launch
+EncPlan plan_encode(const Geometry &g, bool value_aligned = true);
 // payload blocks a chunk of the 8-bit FTL/BASE lane-per-block encoder (k_enc_px.hip) codes: a multiple of four, so that every
 // four-block group of a level-2 restart table entry (five bytes) belongs to one workgroup, which writes it
 constexpr uint32_t PX_NBP = 252;

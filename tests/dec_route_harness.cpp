@@ -328,7 +328,24 @@ void run_group(uint32_t tsz, uint32_t mode, Out &out) {
 }
 }  // namespace
 
+// `plan W H BANDS TSZ MAP ...` (any number of such groups): how plan_encode cuts a common-factor raster into chunks -- blocks a chunk,
+// chunks, which front end codes them and which chunks a sample looks at -- for tests/test_best_carry.py, which aims its rasters at the chunks' seams
+static int print_plans(int argc, char **argv) {
+    for (int i = 2; i + 4 < argc; i += 5) {
+        const uint32_t w = (uint32_t)atoi(argv[i]), h = (uint32_t)atoi(argv[i + 1]), bands = (uint32_t)atoi(argv[i + 2]), tsz = (uint32_t)atoi(argv[i + 3]);
+        const Geometry g = make_geometry(w, h, bands, tsz, CM_BEST, HILBERT, atoi(argv[i + 4]));
+        const EncPlan p = plan_encode(g);
+        printf("plan %u %u %u %u %s nbp=%u nchunks=%u front=%s sampled=", w, h, bands, tsz, argv[i + 4], p.nbp, p.nchunks, p.px ? "px_best" : p.pxw_best ? "pxw_front" : "enc_front");
+        // the chunks a sample looks at, as the sampling kernels take them: best_sample_count of them, evenly spread from chunk 0
+        const uint32_t count = best_sample_count(p.nchunks), step = (p.nchunks + count - 1) / count;
+        for (uint32_t k = 0; k * step < p.nchunks && k < count; k++) printf("%s%u", k ? "," : "", k * step);
+        printf("\n");
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "plan")) return print_plans(argc, argv);
     const char *label = argc > 1 ? argv[1] : "none";
     prof_enable(1);
     static const uint32_t TSZ[] = {1, 2, 4, 8};

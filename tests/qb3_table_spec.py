@@ -62,20 +62,22 @@ KINDS = np.array(["0", "N", "C", "I"])
 _KIND_DIGIT = bytes.maketrans(b"NCI", b"123")
 
 
-def _raw_trace(oracle, img, dtype, mode, cband, fix_b2=False):
+def _raw_trace(oracle, img, dtype, mode, cband, fix_b2=False, encoder=None):
     """(stream int, bits, rows [n, 5] of uint64, band state) of the oracle's raw encode under its trace; a row: start bit, kind (index
-    into KINDS), rung the band is left at, the unit's factor, the band-state factor before it"""
+    into KINDS), rung the band is left at, the unit's factor, the band-state factor before it.  encoder: an oracle.Encoder of the
+    raster's shape to encode with as it stands (its mode, band map and band state), not a fresh one"""
     import ctypes as C
     import tempfile
     lib = oracle.lib
     lib.qb3o_set_trace.argtypes, lib.qb3o_set_trace.restype = [C.c_char_p], None
     h, w, b = img.shape
-    e = oracle.Encoder(w, h, b, dtype)
-    e.set_mode(mode)
-    if cband is not None:
-        e.set_coreband(cband)
-    if fix_b2:                      # (keep the units the reference drops, SURVEY B-2: for a generator that looks for them)
-        lib.qb3o_set_fix_b2(e.p, 1)
+    e = encoder or oracle.Encoder(w, h, b, dtype)
+    if encoder is None:
+        e.set_mode(mode)
+        if cband is not None:
+            e.set_coreband(cband)
+        if fix_b2:                  # (keep the units the reference drops, SURVEY B-2: for a generator that looks for them)
+            lib.qb3o_set_fix_b2(e.p, 1)
     dst = np.zeros(e.max_size() + 64, dtype=np.uint8)
     src = np.ascontiguousarray(img)
     with tempfile.NamedTemporaryFile("rb", suffix=".txt") as f:

@@ -1061,6 +1061,33 @@ def test_unaligned_device_pointers(qb3, oracle, shape, off, mode):
     assert bool((guard[:off] == 0xA5).all()) and bool((guard[off + raw.numel():] == 0xA5).all()), "wrote outside the raster"
 
 
+@pytest.mark.parametrize("mode", [FTL, BASE])
+@pytest.mark.parametrize("case", [(4, 1, 2, "DEM"), (5, 1, 1, "DEM"), (6, 1, 4, "DEM"), (7, 1, 3, "DEM"),
+                                  (2, 1, 1, "LANDSAT16"), (3, 1, 1, "DEM"), (2, 3, 1, "LANDSAT16"), (3, 3, 1, "NOISY3"), (2, 8, 1, "LANDSAT16")],
+                         ids=lambda c: "t%d-x%d-off%d" % c[:3])
+def test_rasters_at_pointers_that_are_not_value_aligned(qb3, oracle, case, mode):
+    """16-bit rasters and 32/64-bit rasters of one band whose source is not aligned to its values cannot go to their lane-per-block
+    kernels: they are planned for the unit-per-lane kernel -- its chunks (a lane a unit, not a lane a block or a band group), its LDS
+    (tile, slot table, rungs, code table).  Rungs below 8 (the code table lies last in that LDS) and from 8 up; several chunks"""
+    import torch
+    from qb3_amd import synth, device as qdev
+    dt, b, off, gen = case
+    w, h = 260, 68
+    img = synth.generate(w, h, b, dt, gen, 6)
+    raw = img.reshape(-1).view(torch.uint8)
+    buf = torch.zeros(raw.numel() + 16, dtype=torch.uint8, device="cuda")
+    src = buf[off:off + raw.numel()]
+    src.copy_(raw)
+    cb = None if b in (1, 3, 4) else list(range(b))
+    enc = qdev.DeviceEncoder(w, h, b, dt, mode=mode, cband=cb)
+    dst, n, index = enc.encode(src)
+    host = img.cpu().numpy().view(oracle.NPTYPE[dt])
+    ref = oracle.encode(host, dt, mode, cband=cb)
+    assert int(ref[10]) == mode, "a coded container, not a stored one"
+    assert n == len(ref) and np.array_equal(dst[:n].cpu().numpy(), ref), first_diff(dst[:n].cpu().numpy(), ref)
+    assert torch.equal(qdev.DeviceDecoder(dst, n).decode(dst, index=index), raw)
+
+
 def test_handles_are_independent_across_threads(qb3, oracle):
     """handles share nothing.  Four host threads, each with its own encoder and decoder handles and its own
     raster, code concurrently (ctypes drops the GIL inside the library); every stream must equal the oracle's"""
