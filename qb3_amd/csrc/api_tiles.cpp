@@ -70,7 +70,7 @@ size_t qb3api::encode_tile_grids(encsp p, const TileGrid *grids, size_t ngrids, 
     Geometry g = make_geometry(p->xsize, p->ysize, p->nbands, p->type, 0, p->order, p->mode, p->cband, nullptr);
     uintptr_t low = 0;                      // a tile of any grid off the alignment of its values: the plan of the kernels that read it
     for (size_t gi = 0; gi < ngrids; gi++) low |= (uintptr_t)grids[gi].img | grids[gi].img_col | grids[gi].img_row;
-    EncPlan plan = plan_encode(g, (low & (tsz - 1)) == 0);      // (no function of the stride: one plan for every grid)
+    EncPlan plan = plan_encode(g, value_aligned_memory(g.tsz, low));      // (no function of the stride: one plan for every grid)
     size_t wsp = (plan.ws_bytes + 255) & ~(size_t)255;
     size_t batch = (size_t)8 << 30 >= wsp ? ((size_t)8 << 30) / wsp : 1;     // keep the workspace under 8 GiB
     if (batch > nmax) batch = nmax;
@@ -109,9 +109,12 @@ size_t qb3api::encode_tile_grids(encsp p, const TileGrid *grids, size_t ngrids, 
             tb.idx_pitch = isz_all; tb.idx_row = d_index ? G.k_row * isz : tb.cols * isz_all;
             uint8_t *out0 = (uint8_t *)d_dst + k0 * dst_pitch;
             if (ix_bytes) ixt.base = out0 + hdr_stamp;
-            void *index_here = !index_all ? nullptr : (d_index ? (uint8_t *)d_index + k0 * isz : (uint8_t *)index_all);
-            if (launch_encode(g, plan, grid_img(G, first), (uint32_t *)(out0 + (hdr & ~(size_t)3)), (uint32_t)(8 * (hdr & 3)), bs,
-                              p->d_ws.p, index_here, st, tb, hdrbuf, (uint32_t)hdr_stamp, ixt)) { p->error = QB3E_LIBERR; return done; }
+            EncJob job;
+            job.img = grid_img(G, first); job.out32 = (uint32_t *)(out0 + (hdr & ~(size_t)3)); job.out_bit0 = (uint32_t)(8 * (hdr & 3));
+            job.st = bs; job.ws = p->d_ws.p; job.tb = tb;
+            job.index = !index_all ? nullptr : (d_index ? (uint8_t *)d_index + k0 * isz : (uint8_t *)index_all);
+            job.hdr = hdrbuf; job.hdr_len = (uint32_t)hdr_stamp; job.ix = ixt;
+            if (launch_encode(g, plan, job, st)) { p->error = QB3E_LIBERR; return done; }
             const uint8_t *dres = (const uint8_t *)p->d_ws.p + plan.ws_bytes - sizeof(EncResult);
             hipError_t e = hipMemcpy2DAsync(res.data(), sizeof(EncResult), dres, wsp, sizeof(EncResult), cnt, hipMemcpyDeviceToHost, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);

@@ -364,22 +364,23 @@ static void launch_enc_best_f(const EncArgs &a, const EncPlan &plan, hipStream_t
     hipLaunchKernelGGL((enc_best_kernel<T, false, FRONT>), dim3(plan.nchunks < 4096 ? plan.nchunks : 4096, a.ntiles), block, plan.lds_bytes, st, a);
 }
 template <typename T>
-static void launch_enc_best_t(const EncArgs &a, const EncPlan &plan, hipStream_t st) {
+static void launch_enc_best_t(const EncArgs &a, const EncPlan &plan, hipStream_t st, bool front) {
     if constexpr (sizeof(T) >= 2) {
         // one band of 16/32/64-bit data (value-aligned pointers): the lane-per-block front end
-        if (plan.pxw_best && ((uintptr_t)a.img & (sizeof(T) - 1)) == 0 && !((a.ts_img | a.tr_img) & (sizeof(T) - 1))) {
+        if (front) {
             if (a.g.order == ZCURVE) launch_enc_best_f<T, 2>(a, plan, st); else launch_enc_best_f<T, 1>(a, plan, st);
             return;
         }
     }
     launch_enc_best_f<T, 0>(a, plan, st);
 }
-void launch_enc_best(const EncArgs &a, const EncPlan &plan, hipStream_t st) {
+// front: EncKernel::best_front, the lane-per-block front end (else EncKernel::best)
+void launch_enc_best(const EncArgs &a, const EncPlan &plan, hipStream_t st, bool front) {
     switch (a.g.tsz) {
-    case 1: launch_enc_best_t<uint8_t>(a, plan, st); break;
-    case 2: launch_enc_best_t<uint16_t>(a, plan, st); break;
-    case 4: launch_enc_best_t<uint32_t>(a, plan, st); break;
-    default: launch_enc_best_t<uint64_t>(a, plan, st); break;
+    case 1: launch_enc_best_t<uint8_t>(a, plan, st, front); break;
+    case 2: launch_enc_best_t<uint16_t>(a, plan, st, front); break;
+    case 4: launch_enc_best_t<uint32_t>(a, plan, st, front); break;
+    default: launch_enc_best_t<uint64_t>(a, plan, st, front); break;
     }
 }
 

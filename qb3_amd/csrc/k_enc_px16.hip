@@ -267,8 +267,8 @@ void launch_enc_px16(const EncArgs &a, const EncPlan &plan, hipStream_t st) {
     switch (plan.px16_bg) {
     case 1: launch_enc_px16_b<1, false>(a, plan, st); break;
     case 2: launch_enc_px16_b<2, false>(a, plan, st); break;
-    case 3: if (plan.px_rgb) launch_enc_px16_b<3, true>(a, plan, st); else launch_enc_px16_b<3, false>(a, plan, st); break;
-    default: if (plan.px_rgb) launch_enc_px16_b<4, true>(a, plan, st); else launch_enc_px16_b<4, false>(a, plan, st); break;
+    case 3: if (plan.rgb) launch_enc_px16_b<3, true>(a, plan, st); else launch_enc_px16_b<3, false>(a, plan, st); break;
+    default: if (plan.rgb) launch_enc_px16_b<4, true>(a, plan, st); else launch_enc_px16_b<4, false>(a, plan, st); break;
     }
 }
 

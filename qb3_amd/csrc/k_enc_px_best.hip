@@ -578,8 +578,8 @@ static void launch_enc_px_best_b(const EncArgs &a, const EncPlan &plan, hipStrea
 }
 void launch_enc_px_best(const EncArgs &a, const EncPlan &plan, hipStream_t st) {
     if (a.g.bands == 1) launch_enc_px_best_b<1, false>(a, plan, st);
-    else if (a.g.bands == 3) { if (plan.px_rgb) launch_enc_px_best_b<3, true>(a, plan, st); else launch_enc_px_best_b<3, false>(a, plan, st); }
-    else { if (plan.px_rgb) launch_enc_px_best_b<4, true>(a, plan, st); else launch_enc_px_best_b<4, false>(a, plan, st); }
+    else if (a.g.bands == 3) { if (plan.rgb) launch_enc_px_best_b<3, true>(a, plan, st); else launch_enc_px_best_b<3, false>(a, plan, st); }
+    else { if (plan.rgb) launch_enc_px_best_b<4, true>(a, plan, st); else launch_enc_px_best_b<4, false>(a, plan, st); }
 }
 
 }  // namespace qb3dev

@@ -294,90 +294,79 @@ static bool pxw_eligible(const Geometry &g, bool best = false) {
     return (g.tsz >= 4 || (best && g.tsz == 2)) && g.bands == 1 && (g.mode == CM_BEST) == best && g.w >= 4 && g.h >= 4 && (g.order == HILBERT || g.order == ZCURVE) && !tuning().no_px;
 }
 
+// The kernel that codes a raster's units (EncKernel, qb3_dev.h): the one place that asks the three rules above for the encoder.  The shapes
+// they take do not overlap -- 8-bit; 16-bit FTL / BASE; one band of 32/64-bit FTL / BASE or of 16/32/64-bit common factor -- so the order of
+// the questions carries no meaning.  rgb, bg, ng: what the chosen kernel's rule says of the band map and the 16-bit split (else false, 0, 0)
+static EncKernel pick_enc_kernel(const Geometry &g, bool value_aligned, bool *rgb, uint32_t *bg, uint32_t *ng) {
+    const bool best = g.mode == CM_BEST;
+    *bg = *ng = 0;
+    if (px_eligible(g, rgb)) return best ? EncKernel::px_best : EncKernel::px;
+    *rgb = false;
+    if (value_aligned && pxw_eligible(g, best)) return best ? EncKernel::best_front : EncKernel::pxw;
+    if (value_aligned && px16_eligible(g, rgb, bg, ng)) return EncKernel::px16;
+    *rgb = false; *bg = *ng = 0;
+    return best ? EncKernel::best : EncKernel::generic;
+}
+
 EncPlan plan_encode(const Geometry &g, bool value_aligned) {
     EncPlan p;
-    const uint32_t dpr = g.bands * g.tsz;
-    p.px = px_eligible(g, &p.px_rgb);
-    p.px16 = false; p.px16_bg = p.px16_ng = 0;
-    p.pxw = false;
-    p.pxw_best = !p.px && value_aligned && pxw_eligible(g, true);        // (same chunks as the generic plan below: one band, slots = threads)
-    if (!p.px && value_aligned && pxw_eligible(g)) {
-        p.pxw = true;
-        p.threads = g.tsz == 8 ? 128 : 256; p.slots = p.threads; p.nbp = p.threads - 1;
-        p.nchunks = (uint32_t)((g.nblocks + p.nbp - 1) / p.nbp);
-        const EncWs L = enc_ws_layout(g, p.nchunks, p.nbp, p.threads);
-        p.lds_bytes = 2048 + 64 + 4 * (size_t)L.slot_dw;
-        p.ws_bytes = L.total;
-        return p;
-    }
-    if (p.px) {
-        p.threads = 256; p.slots = 256; p.nbp = g.mode == CM_BEST ? 255 : PX_NBP;      // (FTL/BASE: whole four-block groups a chunk)
-        p.nchunks = (uint32_t)((g.nblocks + p.nbp - 1) / p.nbp);
-        const EncWs L = enc_ws_layout(g, p.nchunks, p.nbp, p.threads);
-        p.lds_bytes = (g.mode == CM_BEST ? PXB_LDS_FIXED : 2048 + 256) + 4 * (size_t)L.slot_dw;
-        p.ws_bytes = L.total;
-        return p;
-    }
-    bool rgb16 = false;
-    if (value_aligned && px16_eligible(g, &rgb16, &p.px16_bg, &p.px16_ng)) {
-        p.px16 = true; p.px_rgb = rgb16;
-        p.threads = 256; p.slots = 256 / p.px16_ng; p.nbp = p.slots - 1;
-        p.nchunks = (uint32_t)((g.nblocks + p.nbp - 1) / p.nbp);
-        const EncWs L = enc_ws_layout(g, p.nchunks, p.nbp, p.threads);
-        p.lds_bytes = 2048 + 256 + 1024 + 4 * (size_t)L.slot_dw;
-        p.ws_bytes = L.total;
-        return p;
-    }
+    const EncKernel k = p.kernel = pick_enc_kernel(g, value_aligned, &p.rgb, &p.px16_bg, &p.px16_ng);
     p.threads = g.tsz == 8 ? 128 : 256;
-    p.slots = p.threads / g.bands;
-    const uint32_t nbp = p.slots - 1;
-    p.nbp = nbp;
-    p.nchunks = (uint32_t)((g.nblocks + nbp - 1) / nbp);
-    // (the pixel tile and the bit buffer -- of slot_dw dwords, what the common-factor kernels zero -- share their memory: enc_front, qb3_enc_front.h)
-    const size_t outdw = enc_ws_layout(g, p.nchunks, nbp, p.threads).slot_dw, tiledw = 4 * (size_t)p.slots * dpr;
-    p.lds_bytes = 8 * (size_t)p.slots + 4 * std::max(tiledw, (outdw + 1) & ~(size_t)1) + 256 + 1024 + (((size_t)p.slots * g.bands + 7) & ~(size_t)7);
-    if (g.mode == CM_BEST) p.lds_bytes += 8 * (size_t)p.threads + 8 * 16 + 4 * MAXBANDS + 8 + 4 * (size_t)p.slots + 4 * 512;     // the writer board: a value per lane, a ballot per wave, a word per band; a word per block (the index's block table)
+    p.slots = (k == EncKernel::px || k == EncKernel::px_best) ? 256 : k == EncKernel::px16 ? 256 / p.px16_ng : p.threads / g.bands;
+    p.nbp = k == EncKernel::px ? PX_NBP : p.slots - 1;      // (FTL/BASE: whole four-block groups a chunk)
+    p.nchunks = (uint32_t)((g.nblocks + p.nbp - 1) / p.nbp);
+    const EncWs L = enc_ws_layout(g, p.nchunks, p.nbp, p.threads);
+    p.ws_bytes = L.total;
+    const size_t outdw = L.slot_dw;
+    // the writer board: a value per lane, a ballot per wave, a word per band; a word per block (the index's block table)
+    const size_t board = 8 * (size_t)p.threads + 8 * 16 + 4 * MAXBANDS + 8 + 4 * (size_t)p.slots + 4 * 512;
+    switch (k) {
+    case EncKernel::pxw: p.lds_bytes = 2048 + 64 + 4 * outdw; break;
+    case EncKernel::px: p.lds_bytes = 2048 + 256 + 4 * outdw; break;
+    case EncKernel::px_best: p.lds_bytes = PXB_LDS_FIXED + 4 * outdw; break;
+    case EncKernel::px16: p.lds_bytes = 2048 + 256 + 1024 + 4 * outdw; break;
     // (the lane-per-block front end has no tile: scan scratch, the code table, the bit buffer -- of the worst common-factor unit -- and the board)
-    if (p.pxw_best) p.lds_bytes = 256 + 1024 + 4 * (size_t)enc_ws_layout(g, p.nchunks, nbp, p.threads).slot_dw + 8 + 8 * (size_t)p.threads + 8 * 16 + 4 * MAXBANDS + 8 + 4 * (size_t)p.slots + 4 * 512;
-    p.ws_bytes = enc_ws_layout(g, p.nchunks, nbp, p.threads).total;
+    case EncKernel::best_front: p.lds_bytes = 256 + 1024 + 4 * outdw + 8 + board; break;
+    case EncKernel::generic: case EncKernel::best: {
+        // (the pixel tile and the bit buffer -- of slot_dw dwords, what the common-factor kernels zero -- share their memory: enc_front, qb3_enc_front.h)
+        const size_t tiledw = 4 * (size_t)p.slots * g.bands * g.tsz;
+        p.lds_bytes = 8 * (size_t)p.slots + 4 * std::max(tiledw, (outdw + 1) & ~(size_t)1) + 256 + 1024 + (((size_t)p.slots * g.bands + 7) & ~(size_t)7);
+        if (k == EncKernel::best) p.lds_bytes += board;
+        break;
+    }
+    }
     return p;
 }
 
 static void launch_enc_units(const EncArgs &a, const EncPlan &plan, hipStream_t st) {
-    if (a.g.mode == CM_BEST) { if (plan.px && a.g.tsz == 1) launch_enc_px_best(a, plan, st); else launch_enc_best(a, plan, st); }
-    else if (plan.px && a.g.tsz == 1) {
-        ProfScope ps("enc_units", st);
-        launch_enc_px(a, plan, st);
+    switch (plan.kernel) {      // (the common-factor launchers open their own profile scopes)
+    case EncKernel::best: launch_enc_best(a, plan, st, false); break;
+    case EncKernel::best_front: launch_enc_best(a, plan, st, true); break;
+    case EncKernel::px_best: launch_enc_px_best(a, plan, st); break;
+    case EncKernel::px: { ProfScope ps("enc_units", st); launch_enc_px(a, plan, st); break; }
+    case EncKernel::px16: { ProfScope ps("enc_units", st); launch_enc_px16(a, plan, st); break; }
+    case EncKernel::pxw: { ProfScope ps("enc_units", st); launch_enc_pxw(a, plan, st); break; }
+    case EncKernel::generic: { ProfScope ps("enc_units", st); launch_enc_generic(a, plan, st); break; }
     }
-    else if (plan.px16 && a.g.tsz == 2 && ((uintptr_t)a.img & 1) == 0) { ProfScope ps("enc_units", st); launch_enc_px16(a, plan, st); }
-    else if (plan.pxw && ((uintptr_t)a.img & (a.g.tsz - 1)) == 0 && !((a.ts_img | a.tr_img) & (a.g.tsz - 1))) { ProfScope ps("enc_units", st); launch_enc_pxw(a, plan, st); }
-    else { ProfScope ps("enc_units", st); launch_enc_generic(a, plan, st); }
-}
-static int launch_encode_all(const EncArgs &a, const EncPlan &plan, hipStream_t st) {
-    launch_enc_units(a, plan, st);
-    launch_enc_post(a, plan, st);
-    HIPCHK(hipGetLastError());
-    return 0;
 }
 
-// the argument block of the encoder kernels (workspace carve, index view, table layout)
-static bool make_enc_args(EncArgs &a, const Geometry &g, const EncPlan &plan, const void *img, uint32_t *out32, uint32_t out_bit0,
-                          const BandState &st_in, void *ws, void *index, const TileBatch &tb,
-                          const uint8_t *hdr, uint32_t hdr_len, const IxTable &ix, bool zrun_probe) {
-    a.zrun_probe = zrun_probe ? 1u : 0u;
+// the argument block of the encoder kernels (workspace carve, index view, table layout); false, with nothing enqueued: the job is refused
+static bool make_enc_args(EncArgs &a, const Geometry &g, const EncPlan &plan, const EncJob &job) {
+    const IxTable &ix = job.ix;
+    a.zrun_probe = job.zrun_probe ? 1u : 0u;
     a.ix_dst = ix.base; a.ix_K = ix.K; a.ix_E = ix.entry_bytes; a.ix_per_chunk = ix.per_chunk; a.ix_blocks = ix.blocks;
     a.ix_spe = g.seg_blocks ? ix.blocks / g.seg_blocks : 0;
-    const TileGridRule tg = make_tile_grid(tb);
-    a.ntiles = tb.n ? tb.n : 1; a.ts_img = tg.src; a.ts_out = tg.dst; a.ts_ws = tb.ws_pitch; a.ts_idx = tg.idx;
+    const TileGridRule tg = make_tile_grid(job.tb);
+    a.ntiles = job.tb.n ? job.tb.n : 1; a.ts_img = tg.src; a.ts_out = tg.dst; a.ts_ws = job.tb.ws_pitch; a.ts_idx = tg.idx;
     a.tcols = tg.cols; a.tmagic = tg.magic; a.tr_img = tg.src_row; a.tr_out = tg.dst_row; a.tr_idx = tg.idx_row;
-    a.hdr_len = hdr_len <= sizeof(a.hdr) ? hdr_len : 0;
+    a.hdr_len = job.hdr_len <= sizeof(a.hdr) ? job.hdr_len : 0;
     a.hdr_back = a.hdr_len + (ix.base ? (uint32_t)ix_total_bytes(ix) + 2 : 0);
-    for (uint32_t i = 0; i < a.hdr_len; i++) a.hdr[i] = hdr[i];
-    a.g = g; a.img = img; a.out32 = out32; a.out_bit0 = out_bit0;
+    for (uint32_t i = 0; i < a.hdr_len; i++) a.hdr[i] = job.hdr[i];
+    a.g = g; a.img = job.img; a.out32 = job.out32; a.out_bit0 = job.out_bit0;
     a.slots = plan.slots; a.nchunks = plan.nchunks; a.dpr = g.bands * g.tsz;
     a.chunk0 = 0; a.chunk_end = plan.nchunks; a.finish_what = 3;
     a.magic_dpr = magic_div(a.dpr); a.magic_bands = magic_div(g.bands);
-    uint8_t *w = (uint8_t *)ws;
+    uint8_t *w = (uint8_t *)job.ws;
     const EncWs L = enc_ws_layout(g, plan.nchunks, plan.nbp, plan.threads);
     a.chunk_bits = (uint32_t *)(w + L.bits);
     a.chunk_off = (uint64_t *)(w + L.off);
@@ -387,29 +376,33 @@ static bool make_enc_args(EncArgs &a, const Geometry &g, const EncPlan &plan, co
     a.cw_has = w + L.cwhas; a.cw_val = (uint64_t *)(w + L.cwval); a.centry = (uint64_t *)(w + L.centry); a.centry_parts = (uint32_t *)(w + L.cparts); a.recode_n = a.centry_parts + 32 * MAXBANDS;
     a.cw_used = w + L.cwused; a.seg_from_entry = w + L.segfe; a.recode_need = (uint32_t *)(w + L.rneed); a.recode_list = (uint32_t *)(w + L.rlist);
     a.slot_dw = L.slot_dw;
-    a.px_ng = plan.px16 ? plan.px16_ng : 1; a.px_magic_ng = magic_div(a.px_ng);
+    a.px_ng = plan.kernel == EncKernel::px16 ? plan.px16_ng : 1; a.px_magic_ng = magic_div(a.px_ng);
     a.px16_bg = g.tsz == 2 ? px16_bands_per_lane(g) : 0;
-    a.px_aligned = !(g.w & 3) && !((g.stride * g.tsz) & 3) && !((uintptr_t)img & 3) && !(tile_pitch_bits(tg, false) & 3);
+    a.px_aligned = !(g.w & 3) && !((g.stride * g.tsz) & 3) && !((uintptr_t)job.img & 3) && !(tile_pitch_bits(tg, false) & 3);
     a.res = (EncResult *)(w + L.res);
-    a.st = st_in;
+    a.st = job.st;
     a.ix_bl = ix.base && ix.block_lens;
     // the 8-bit FTL/BASE lane-per-block coder writes a level-2 table itself (entry = index segment of 64 blocks); the library's own
     // index is then not needed at all
-    a.ix_coder = a.ix_bl && plan.px && g.tsz == 1 && g.mode != CM_BEST && g.seg_blocks == 64 && ix.blocks == 64;
+    a.ix_coder = a.ix_bl && plan.kernel == EncKernel::px && g.seg_blocks == 64 && ix.blocks == 64;
     a.ix_wgs = 0;
-    a.have_idx = index != nullptr && !(a.ix_coder && ix.own_index);
-    a.idx_no_ulen = index && ix.base && ix.own_index && !ix.block_lens;      // (block lengths are sums of the unit lengths)
-    a.idx = index ? index_view(g, index) : IndexView{nullptr, nullptr, nullptr, nullptr, nullptr};
+    a.have_idx = job.index != nullptr && !(a.ix_coder && ix.own_index);
+    a.idx_no_ulen = job.index && ix.base && ix.own_index && !ix.block_lens;      // (block lengths are sums of the unit lengths)
+    a.idx = job.index ? index_view(g, job.index) : IndexView{nullptr, nullptr, nullptr, nullptr, nullptr};
     if (g.tsz != 1 && g.tsz != 2 && g.tsz != 4 && g.tsz != 8) { set_error("encode: bad value size", 0); return false; }
+    // a plan made for value-aligned memory (plan_encode) and memory that is not: another kernel would need another plan
+    const bool reads_values = plan.kernel == EncKernel::px16 || plan.kernel == EncKernel::pxw || plan.kernel == EncKernel::best_front;
+    if (reads_values && !value_aligned_memory(g.tsz, (uintptr_t)job.img | tile_pitch_bits(tg, false))) { set_error("encode: the plan's kernel needs value-aligned memory", 0); return false; }
     return true;
 }
 
-int launch_encode(const Geometry &g, const EncPlan &plan, const void *img, uint32_t *out32, uint32_t out_bit0,
-                  const BandState &st_in, void *ws, void *index, void *stream, const TileBatch &tb,
-                  const uint8_t *hdr, uint32_t hdr_len, const IxTable &ix, bool zrun_probe) {
+int launch_encode(const Geometry &g, const EncPlan &plan, const EncJob &job, void *stream) {
     EncArgs a;
-    if (!make_enc_args(a, g, plan, img, out32, out_bit0, st_in, ws, index, tb, hdr, hdr_len, ix, zrun_probe)) return -1;
-    return launch_encode_all(a, plan, (hipStream_t)stream);
+    if (!make_enc_args(a, g, plan, job)) return -1;
+    launch_enc_units(a, plan, (hipStream_t)stream);
+    launch_enc_post(a, plan, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 // ---- a pipelined host call codes the raster strip by strip: a strip is a scan group of chunks (SCAN_GROUP of them), coded,
@@ -425,23 +418,20 @@ const uint64_t *encode_strip_total(const Geometry &g, const EncPlan &plan, void 
     const EncWs L = enc_ws_layout(g, plan.nchunks, plan.nbp, plan.threads);
     return (const uint64_t *)((uint8_t *)ws + L.gsum) + strip + 1;
 }
-int launch_encode_strip(const Geometry &g, const EncPlan &plan, const void *img, uint32_t *out32, uint32_t out_bit0,
-                        const BandState &st_in, void *ws, void *index, void *stream, const uint8_t *hdr, uint32_t hdr_len, const IxTable &ix, uint32_t strip) {
+int launch_encode_strip(const Geometry &g, const EncPlan &plan, const EncJob &job, void *stream, uint32_t strip) {
     EncArgs a;
-    if (!make_enc_args(a, g, plan, img, out32, out_bit0, st_in, ws, index, TileBatch(), hdr, hdr_len, ix, false)) return -1;
+    if (!make_enc_args(a, g, plan, job)) return -1;
     a.chunk0 = strip * SCAN_GROUP;
     a.chunk_end = std::min<uint32_t>(plan.nchunks, a.chunk0 + SCAN_GROUP);
     a.finish_what = 1;
-    hipStream_t st = (hipStream_t)stream;
-    launch_enc_units(a, plan, st);
-    launch_enc_post_strip(a, plan, st, strip);
+    launch_enc_units(a, plan, (hipStream_t)stream);
+    launch_enc_post_strip(a, plan, (hipStream_t)stream, strip);
     HIPCHK(hipGetLastError());
     return 0;
 }
-int launch_encode_tail(const Geometry &g, const EncPlan &plan, const void *img, uint32_t *out32, uint32_t out_bit0,
-                       const BandState &st_in, void *ws, void *index, void *stream, const uint8_t *hdr, uint32_t hdr_len, const IxTable &ix) {
+int launch_encode_tail(const Geometry &g, const EncPlan &plan, const EncJob &job, void *stream) {
     EncArgs a;
-    if (!make_enc_args(a, g, plan, img, out32, out_bit0, st_in, ws, index, TileBatch(), hdr, hdr_len, ix, false)) return -1;
+    if (!make_enc_args(a, g, plan, job)) return -1;
     a.finish_what = 2;
     launch_enc_post_tail(a, plan, (hipStream_t)stream);
     HIPCHK(hipGetLastError());

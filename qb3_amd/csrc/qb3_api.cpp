@@ -165,17 +165,19 @@ static size_t stored_encode_host(encsp p, const void *source, void *destination)
 static bool encode_blocks_device(encsp p, const Geometry &g, const void *d_img, uint8_t *d_out, size_t hdr,
                                  void *d_index, hipStream_t st, bool carry, uint64_t *bits, const uint8_t *hdrbytes,
                                  size_t hdr_stamp, const IxTable &ix, int *zero_run = nullptr) {
-    EncPlan plan = plan_encode(g, ((uintptr_t)d_img & (g.tsz - 1)) == 0);
+    EncPlan plan = plan_encode(g, value_aligned_memory(g.tsz, (uintptr_t)d_img));
     if (!p->d_ws.ensure(plan.ws_bytes)) return false;
-    BandState bs;
-    memset(&bs, 0, sizeof(bs));
+    EncJob job;
+    memset(&job.st, 0, sizeof(job.st));
     for (size_t c = 0; c < p->nbands; c++) {
-        bs.prev[c] = p->band[c].prev; bs.cf[c] = p->band[c].cf; bs.rung[c] = (uint8_t)p->band[c].runbits;
+        job.st.prev[c] = p->band[c].prev; job.st.cf[c] = p->band[c].cf; job.st.rung[c] = (uint8_t)p->band[c].runbits;
     }
-    uint32_t *out32 = (uint32_t *)(d_out + (hdr & ~(size_t)3));
+    job.img = d_img; job.out32 = (uint32_t *)(d_out + (hdr & ~(size_t)3)); job.out_bit0 = (uint32_t)(8 * (hdr & 3));
+    job.ws = p->d_ws.p; job.index = d_index;
+    job.hdr = hdrbytes; job.hdr_len = (uint32_t)hdr_stamp; job.ix = ix; job.zrun_probe = zero_run != nullptr;
     EncResult res;
     const uint8_t *dres = (const uint8_t *)p->d_ws.p + plan.ws_bytes - sizeof(EncResult);
-    if (launch_encode(g, plan, d_img, out32, (uint32_t)(8 * (hdr & 3)), bs, p->d_ws.p, d_index, st, TileBatch(), hdrbytes, (uint32_t)hdr_stamp, ix, zero_run != nullptr)) return false;
+    if (launch_encode(g, plan, job, st)) return false;
     const hipError_t e = fetch_small(&res, dres, sizeof(res), st);
     if (e != hipSuccess) { set_error("encode kernels", (int)e); return false; }
     prof_collect();
@@ -219,11 +221,13 @@ static int encode_pipelined(encsp p, const Geometry &g, const void *host_src, vo
     if (nstrips < 3 || nstrips + 64 > Pipe::WORDS) return 0;
     if (!p->pipe.init() || !p->pipe.events((size_t)nstrips + 1) || !p->stager.init() || !p->stager2.init()) return 0;
     if (!p->d_img.ensure(src_bytes) || !p->d_ws.ensure(plan.ws_bytes)) { p->error = QB3E_LIBERR; return -1; }
-    BandState bs;
-    memset(&bs, 0, sizeof(bs));
-    for (size_t c = 0; c < p->nbands; c++) { bs.prev[c] = p->band[c].prev; bs.cf[c] = p->band[c].cf; bs.rung[c] = (uint8_t)p->band[c].runbits; }
-    uint32_t *out32 = (uint32_t *)(out_dev + (hdr & ~(size_t)3));
     const uint32_t out_bit0 = (uint32_t)(8 * (hdr & 3));
+    EncJob job;             // of every strip and of the tail
+    memset(&job.st, 0, sizeof(job.st));
+    for (size_t c = 0; c < p->nbands; c++) { job.st.prev[c] = p->band[c].prev; job.st.cf[c] = p->band[c].cf; job.st.rung[c] = (uint8_t)p->band[c].runbits; }
+    job.img = p->d_img.p; job.out32 = (uint32_t *)(out_dev + (hdr & ~(size_t)3)); job.out_bit0 = out_bit0;
+    job.ws = p->d_ws.p; job.index = d_index;
+    job.hdr = hdrbuf; job.hdr_len = (uint32_t)hdr_stamp; job.ix = ixt;
     // raster bytes a strip needs in device memory: the rows of its last block (the block before its first one is in the strip before)
     std::vector<size_t> need(nstrips);
     for (uint32_t s = 0; s < nstrips; s++) {
@@ -272,10 +276,10 @@ static int encode_pipelined(encsp p, const Geometry &g, const void *host_src, vo
                 e = hipEventRecord(ev_u, sU);
                 if (e == hipSuccess) e = hipStreamWaitEvent(sK, ev_u, 0);
                 if (e != hipSuccess) break;
-                if (launch_encode_strip(g, plan, p->d_img.p, out32, out_bit0, bs, p->d_ws.p, d_index, sK, hdrbuf, (uint32_t)hdr_stamp, ixt, next_strip)) { launch_failed = true; break; }
+                if (launch_encode_strip(g, plan, job, sK, next_strip)) { launch_failed = true; break; }
                 e = hipMemcpyAsync(&totals[next_strip], encode_strip_total(g, plan, p->d_ws.p, next_strip), 8, hipMemcpyDeviceToHost, sK);
                 if (e == hipSuccess && next_strip + 1 == nstrips) {        // behind the last strip: index positions, the table, the result words
-                    if (launch_encode_tail(g, plan, p->d_img.p, out32, out_bit0, bs, p->d_ws.p, d_index, sK, hdrbuf, (uint32_t)hdr_stamp, ixt)) { launch_failed = true; break; }
+                    if (launch_encode_tail(g, plan, job, sK)) { launch_failed = true; break; }
                     e = hipMemcpyAsync(res_host, dres, sizeof(EncResult), hipMemcpyDeviceToHost, sK);
                 }
                 if (e == hipSuccess) e = hipEventRecord(p->pipe.ev[next_strip], sK);

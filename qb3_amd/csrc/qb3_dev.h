@@ -1,5 +1,5 @@
-// qb3_amd/csrc/qb3_dev.h -- internal interface between the host API (qb3_api.cpp) and the HIP kernels
-// (qb3_kernels.hip).  Nothing here is exported from the shared library.
+// qb3_amd/csrc/qb3_dev.h -- internal interface between the host API (qb3_api.cpp, api_*.cpp) and the HIP kernels
+// (k_*.hip; their host side: k_host.hip, k_dec_launch.hip).  Nothing here is exported from the shared library.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -113,24 +113,34 @@ inline bool rle0_no_uniform_chunk(const EncResult &r, uint64_t min_chunk_bytes) 
     return shared < 1000 && r.zero_dwords < 1022 - shared && r.ff_pairs < 1024;
 }
 
-// Workspace sizes
+// The kernel that codes the units of a raster.  pick_enc_kernel (k_host.hip) is the one place that says which: plan_encode asks it, the
+// plan carries the answer, and everything behind the plan -- sizes, arguments, the launch -- reads plan.kernel.
+//   generic     a unit per lane, FTL / BASE (k_enc_generic.hip)            best        ... common factor (k_enc_best.hip, FRONT 0)
+//   px          8-bit, 1/3/4 bands: a lane per block (k_enc_px.hip)        px_best     ... common factor (k_enc_px_best.hip)
+//   px16        16-bit: a lane per block and band group (k_enc_px16.hip)
+//   pxw         32/64-bit, one band: a lane per block (k_enc_pxw.hip)      best_front  16/32/64-bit, one band, common factor: k_enc_best.hip
+//                                                                                      behind its lane-per-block front end (FRONT 1 Hilbert, 2 Z curve)
+// px16, pxw and best_front read values at their natural alignment: they need value-aligned memory.
+enum class EncKernel { generic, px, px16, pxw, best, best_front, px_best };
+// value-aligned memory: the image pointer and the pitches between tiles, OR-ed into `bits`, are multiples of the value size.  What the
+// callers of plan_encode ask of the memory they will launch with, and what make_enc_args checks of the memory a launch is given
+inline bool value_aligned_memory(uint32_t tsz, uint64_t bits) { return (bits & (tsz - 1)) == 0; }
+
+// How a raster is coded: the kernel, its workgroups and its workspace
 struct EncPlan {
+    EncKernel kernel;
+    bool rgb;               // px, px_best, px16: the default R-G,G,B-G map (else identity)
+    uint32_t px16_bg, px16_ng;      // px16: bands per lane (1..4), lanes per block (else 0)
     uint32_t threads;       // workgroup size = units per chunk (incl. halo units)
     uint32_t slots;         // block slots per chunk, slot 0 is the halo block
+    uint32_t nbp;           // payload blocks per chunk
     uint32_t nchunks;
     size_t lds_bytes;
     size_t ws_bytes;        // chunk counts/offsets, seam table, per-chunk scratch slots, EncResult (last)
-    uint32_t nbp;           // payload blocks per chunk
-    bool px;                // 8-bit 1/3/4-band register-resident kernel applies (lane per block; also for the common-factor modes: k_enc_px_best.hip)
-    bool px_rgb;            //   ... with the default R-G,G,B-G map (else identity)
-    bool px16;              // 16-bit register-resident kernel applies (lane per block and band group)
-    uint32_t px16_bg, px16_ng;      //   ... bands per lane (1..4), lanes per block
-    bool pxw;               // 32/64-bit single-band register-resident kernel applies (lane per block; k_enc_pxw.hip)
-    bool pxw_best;          // ... its front end under the common-factor analysis (k_enc_best.hip, FRONT = 1 / 2)
 };
-// value_aligned: the source pointer and the pitches between tiles are multiples of the value size.  Where they are not, the 16-bit and
-// one-band 32/64-bit lane-per-block kernels cannot read the raster and the plan is the unit-per-lane kernels' own -- their chunks, their
-// LDS -- not a lane-per-block plan handed to another kernel at launch
+// value_aligned: as above, of the memory the launches will get.  Where it is not, the 16-bit and one-band 16/32/64-bit lane-per-block
+// kernels cannot read the raster and the plan is the unit-per-lane kernels' own -- their chunks, their LDS.  A plan made for aligned
+// memory and launched with other memory is refused (make_enc_args, k_host.hip), not handed to another kernel
 EncPlan plan_encode(const Geometry &g, bool value_aligned = true);
 // payload blocks a chunk of the 8-bit FTL/BASE lane-per-block encoder (k_enc_px.hip) codes: a multiple of four, so that every
 // four-block group of a level-2 restart table entry (five bytes) belongs to one workgroup, which writes it
@@ -196,20 +206,23 @@ size_t walk_table_cap();                // what a decoder allocates at most (1 G
 struct DecPlan;
 bool walk_table_applies(const Geometry &g, const DecPlan &plan);
 
-// Encode the block stream of one image.  All pointers are device pointers.
-//   img        image, g.tsz-byte values
-//   out32      4-byte aligned address at or below the first stream byte
-//   out_bit0   bit offset of the first stream bit relative to out32 (multiple of 8, < 32)
-//   st_in      initial band state (host copy, passed by value to the kernels)
-//   ws         workspace of plan.ws_bytes; the EncResult is its LAST sizeof(EncResult) bytes
-//   index      optional decode index (nullptr = none)
-// Launches on `stream`, does not synchronise.  Returns hipError_t as int.
-// ix: base == nullptr when no table is wanted
-int launch_encode(const Geometry &g, const EncPlan &plan, const void *img, uint32_t *out32, uint32_t out_bit0,
-                  const BandState &st_in, void *ws, void *index, void *stream, const TileBatch &tb = TileBatch(),
-                  const uint8_t *hdr = nullptr, uint32_t hdr_len = 0,      // hdr: container header stamped before each stream
-                  const IxTable &ix = IxTable(),
-                  bool zrun_probe = false);     // count runs of zero bytes and pairs of 0xff while concatenating (EncResult::zero_run, ff_pairs)
+// Encode the block stream of one image: what a launch codes, from where, to where.  All pointers are device pointers.
+struct EncJob {
+    const void *img = nullptr;      // image, g.tsz-byte values
+    uint32_t *out32 = nullptr;      // 4-byte aligned address at or below the first stream byte
+    uint32_t out_bit0 = 0;          // bit offset of the first stream bit relative to out32 (multiple of 8, < 32)
+    BandState st;                   // initial band state (host copy, passed by value to the kernels)
+    void *ws = nullptr;             // workspace of plan.ws_bytes; the EncResult is its LAST sizeof(EncResult) bytes
+    void *index = nullptr;          // optional decode index (nullptr = none)
+    TileBatch tb;
+    const uint8_t *hdr = nullptr;   // container header stamped before each stream
+    uint32_t hdr_len = 0;
+    IxTable ix;                     // base == nullptr when no table is wanted
+    bool zrun_probe = false;        // count runs of zero bytes and pairs of 0xff while concatenating (EncResult::zero_run, ff_pairs)
+};
+// Launches on `stream`, does not synchronise.  Returns hipError_t as int; -1, with nothing enqueued, for a value size that is none, or
+// when the plan's kernel needs value-aligned memory and job.img or a tile pitch is not
+int launch_encode(const Geometry &g, const EncPlan &plan, const EncJob &job, void *stream);
 
 // Strips of a pipelined host call (k_host.hip): can this coding be cut into strips; how many; blocks of the raster a strip and
 // its predecessors cover (what must be in device memory before it is coded); where the running stream length behind a strip is
@@ -217,10 +230,8 @@ bool encode_strips_ok(const Geometry &g, const EncPlan &plan);
 uint32_t encode_strip_count(const EncPlan &plan);
 uint64_t encode_strip_blocks(const EncPlan &plan, uint32_t strip);
 const uint64_t *encode_strip_total(const Geometry &g, const EncPlan &plan, void *ws, uint32_t strip);
-int launch_encode_strip(const Geometry &g, const EncPlan &plan, const void *img, uint32_t *out32, uint32_t out_bit0,
-                        const BandState &st_in, void *ws, void *index, void *stream, const uint8_t *hdr, uint32_t hdr_len, const IxTable &ix, uint32_t strip);
-int launch_encode_tail(const Geometry &g, const EncPlan &plan, const void *img, uint32_t *out32, uint32_t out_bit0,
-                       const BandState &st_in, void *ws, void *index, void *stream, const uint8_t *hdr, uint32_t hdr_len, const IxTable &ix);
+int launch_encode_strip(const Geometry &g, const EncPlan &plan, const EncJob &job, void *stream, uint32_t strip);
+int launch_encode_tail(const Geometry &g, const EncPlan &plan, const EncJob &job, void *stream);
 
 // What decodes a raster.  The bool flags say that a kernel APPLIES to the geometry (plan_decode); which one a launch uses, given the
 // pointers it gets, is decided in one place: pick_dec_kernel (k_dec_launch.hip), and what runs in front of it next to that (DecFront).

@@ -639,7 +639,7 @@ uint32_t max_unit_bits(uint32_t tsz, uint32_t mode = CM_FTL);
 
 // launchers, one per translation unit; they enqueue on `st` and return nothing (errors surface through hipGetLastError)
 void launch_enc_generic(const EncArgs &a, const EncPlan &plan, hipStream_t st);    // k_enc_generic.hip
-void launch_enc_best(const EncArgs &a, const EncPlan &plan, hipStream_t st);       // k_enc_best.hip
+void launch_enc_best(const EncArgs &a, const EncPlan &plan, hipStream_t st, bool front);   // k_enc_best.hip (front: its lane-per-block front end)
 void launch_enc_px(const EncArgs &a, const EncPlan &plan, hipStream_t st);         // k_enc_px.hip
 void launch_enc_px_best(const EncArgs &a, const EncPlan &plan, hipStream_t st);    // k_enc_px_best.hip
 void launch_enc_px16(const EncArgs &a, const EncPlan &plan, hipStream_t st);       // k_enc_px16.hip

@@ -40,10 +40,9 @@ def _objects(objdir, must_exist):
     return [p for p in paths if p not in missing]
 
 
-def _build(objs, workdir):
+def _build(objs, workdir, source=os.path.join(ROOT, "tests", "dec_route_harness.cpp"), include=CSRC):
     exe = os.path.join(workdir, "dec_route_harness")
-    subprocess.run([HIPCC, "-x", "hip", "--cuda-host-only", "-O2", "-std=c++17", "-fPIC", "-I", CSRC, "-c", os.path.join(ROOT, "tests", "dec_route_harness.cpp"),
-                    "-o", exe + ".o"], check=True, capture_output=True)
+    subprocess.run([HIPCC, "-x", "hip", "--cuda-host-only", "-O2", "-std=c++17", "-fPIC", "-I", include, "-c", source, "-o", exe + ".o"], check=True, capture_output=True)
     subprocess.run(["g++", exe + ".o"] + objs + ["-o", exe, "-lpthread"], check=True, capture_output=True)      # (no HIP runtime: every entry point is the harness's)
     return exe
 
@@ -57,14 +56,17 @@ def _signature(block):
     return "\n".join(sig)
 
 
-def run_all(objs, workdir):
-    """(text of dec_routes.fnv, text of dec_routes.txt) from one run of the harness per switch setting, all at once"""
-    exe = _build(objs, workdir)
+def run_all(objs, workdir, mode=(), switches=None, signature=None, exe=None):
+    """(text of dec_routes.fnv, text of dec_routes.txt) from one run of the harness per switch setting, all at once.  With a mode, switches
+    and a signature of its own tests/test_encode_routes.py gets the encoder's two texts from here; run I's whole output stays in
+    workdir/runI.txt"""
+    switches, signature = switches or SWITCHES, signature or _signature
+    exe = exe or _build(objs, workdir)
     base = {k: v for k, v in os.environ.items() if not k.startswith("QB3_")}
-    logs = [open(os.path.join(workdir, "run%d.txt" % i), "w+") for i in range(len(SWITCHES))]      # (files, not pipes: no run waits for a reader)
-    procs = [subprocess.Popen([exe, name], env=dict(base, **env), stdout=log) for (name, env), log in zip(SWITCHES, logs)]
+    logs = [open(os.path.join(workdir, "run%d.txt" % i), "w+") for i in range(len(switches))]      # (files, not pipes: no run waits for a reader)
+    procs = [subprocess.Popen([exe] + list(mode) + [name], env=dict(base, **env), stdout=log) for (name, env), log in zip(switches, logs)]
     fnv, routes, seen = [], [], set()
-    for (name, _), p, log in zip(SWITCHES, procs, logs):
+    for (name, _), p, log in zip(switches, procs, logs):
         assert p.wait() == 0, "the harness failed under switch %s" % name
         log.seek(0)
         out = log.read()
@@ -72,8 +74,8 @@ def run_all(objs, workdir):
         fnv += [line for line in out.splitlines() if line.startswith("fnv ")]
         routes.append("## switch %s: the launch sequences no setting above has shown\n" % name)
         for block in out.split("\n\n"):
-            if block.startswith("case ") and _signature(block) not in seen:
-                seen.add(_signature(block))
+            if block.startswith("case ") and signature(block) not in seen:
+                seen.add(signature(block))
                 routes.append(block + "\n")
     return "\n".join(fnv) + "\n", "\n".join(routes)
 
